@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W          (N=1: run directly)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N>1)
+    python bench.py ... --full                              (the headline plus every extra object listed below)
+    python bench.py ... --dump-outputs DIR                  (also write the last timed step's outputs as DIR/<name>.npy)
 
 One "step" = one forward + one full backward of the rasterizer through the public API
 (GaussianRasterizer -> autograd -> ctypes -> C ABI -> HIP kernels) on one synthetic scene that is
@@ -12,7 +14,8 @@ stand-in is used and labelled as such.  With N>1 every rank rasterizes its own s
 GPU, no collective inside the raster path; RCCL only for the barriers and the final reduction):
 weak scaling, value = (N * K) / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline: metric, value, unit, ms_per_step, dtype, config.
+Extra objects on the JSON line, measured only with --full:
   roofline     -- for the dominant kernel stage: algorithmic bytes (SURVEY 8(d) per-unit figures x the
                   units one launch processes) / average launch duration measured live with HIP events
                   on the launch stream (gsr_profile_* in the C ABI), against the 8 TB/s HBM peak.
@@ -846,7 +849,7 @@ def strict_parity_row(args):
         return {"error": "libgsraster_precise.so is not built"}
     env = dict(os.environ, GSR_LIB=lib)
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", "30", "--warmup", "5", "--cpu-budget", "0.1",
-           "--no-next-rows", "--no-strict-parity"]  # (--cpu-budget 0.1: one oracle iteration, for its parity_check)
+           "--full", "--no-next-rows", "--no-strict-parity"]  # (--cpu-budget 0.1: one oracle iteration, for its parity_check)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if p.returncode != 0 or not lines:
@@ -995,6 +998,13 @@ class SceneBench:
         self.P, self.W, self.H = P, W, H
         self._t = t
         self.rot = None
+        self.last = None  # what the most recent step handed back to its caller (--dump-outputs)
+
+    def _keep(self, color, depth, feat, radii, grads):
+        # detached: holding the outputs must not keep the step's autograd graph (and its workspaces) alive
+        self.last = {"color": color.detach(), "depth": depth.detach(), "uncertainty": feat.detach(), "radii": radii,
+                     **{"grad_" + k: g for k, g in zip(("means3D", "opacities", "uncertainties", "colors", "scales", "rotations",
+                                                        "means2D"), grads)}}
 
     def make_rotation(self, V, seed=7, angle=0.03, eps_pos=2e-4, eps_op=1e-3):
         """Training-like view rotation (train.py:414-416 pops a shuffled stack of cameras, one per iteration, and the
@@ -1025,7 +1035,17 @@ class SceneBench:
         noise = [(torch.randn(self.leaves[0].shape, device=self.leaves[0].device, generator=g),
                   torch.randn(self.leaves[1].shape, device=self.leaves[1].device, generator=g)) for _ in range(4)]
         rng = np.random.default_rng(seed)
-        self.rot = {"V": V, "rasts": rasts, "noise": noise, "rng": rng, "order": [], "k": 0, "eps": (eps_pos, eps_op), "angle": angle}
+        self.rot = {"V": V, "rasts": rasts, "noise": noise, "rng": rng, "order": [], "k": 0, "eps": (eps_pos, eps_op), "angle": angle,
+                    "seed": seed, "start": [x.detach().clone() for x in self.leaves[:2]]}
+
+    def rewind_rotation(self):
+        """Back to where make_rotation started: the unperturbed Gaussians, the first view of the first epoch.  The warm-up runs for a
+        time, not a number of steps, so without this the timed steps would start from a cloud and a view that vary from run to run."""
+        r = self.rot
+        with torch.no_grad():
+            for x, x0 in zip(self.leaves[:2], r["start"]):
+                x.copy_(x0)
+        r["order"], r["k"], r["rng"] = [], 0, np.random.default_rng(r["seed"])
 
     def step_rot(self, perturb=True):
         """One training-like iteration: pop the next view of the shuffled epoch, move the Gaussians, forward + backward."""
@@ -1045,7 +1065,7 @@ class SceneBench:
         color, depth, feat, radii = r["rasts"][v](means3D, self.means2D, opac, unc, colors_precomp=colors, scales=scales, rotations=rots)
         outs = [o for o, use in zip((color, depth, feat), self.gsel) if use]
         gos = [g for g, use in zip(self.g, self.gsel) if use]
-        torch.autograd.grad(outs, self.inputs, gos)
+        self._keep(color, depth, feat, radii, torch.autograd.grad(outs, self.inputs, gos))
         return radii
 
     def step(self):
@@ -1053,7 +1073,8 @@ class SceneBench:
         color, depth, feat, radii = self.rast(means3D, self.means2D, opac, unc, colors_precomp=colors, scales=scales, rotations=rots)
         outs = [o for o, use in zip((color, depth, feat), self.gsel) if use]
         gos = [g for g, use in zip(self.g, self.gsel) if use]
-        torch.autograd.grad(outs, self.inputs, gos)  # maps the loss does not use get no gradient, as in training
+        grads = torch.autograd.grad(outs, self.inputs, gos)  # maps the loss does not use get no gradient, as in training
+        self._keep(color, depth, feat, radii, grads)
         return radii
 
     def check(self):
@@ -1138,6 +1159,8 @@ def run_config5(args, dist, dev, rank, world):
     for rec, sb in zip(mine, kept):  # untimed, after the job: each scene's outputs satisfy the rasterizer's identities on this rank's data
         ok, detail = sb.check()
         rec.update(check_ok=bool(ok), check={k: (v if isinstance(v, bool) else float(f"{v:.3g}")) for k, v in detail.items()})
+    if rank == 0 and args.dump_outputs and kept:  # (the last timed step of the last scene this rank ran; the checks above keep sb.last)
+        dump_outputs(args.dump_outputs, kept[-1].last, kept[-1].P)
     del kept, resident
     per_rank = multi.gather_objects(dist, {"rank": rank, "device": int(dev.index), "scenes": [r["scene"] for r in mine], "busy_s": round(busy, 4),
                                            "build_all_scenes_s": round(build_s, 2), "numa": NUMA_INFO})
@@ -1174,6 +1197,28 @@ def run_config5(args, dist, dev, rank, world):
         print(json.dumps(out), flush=True)
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs writes at most this much (npy headers come on top: well under 64 MB in all)
+
+
+def dump_outputs(path, last, P):
+    """--dump-outputs: the arrays the last timed step handed back to its caller (images, radii, the gradients of the seven leaves) as
+    float32 `<name>.npy` under `path`.  Images are written whole; per-Gaussian arrays as the same rows of each, a fixed seeded sample
+    when all P rows would not fit the budget, with their row numbers in `gaussian_index.npy` (float64)."""
+    os.makedirs(path, exist_ok=True)
+    images = {k: v for k, v in last.items() if k in ("color", "depth", "uncertainty")}
+    per_gauss = {k: v for k, v in last.items() if k not in images}  # radii and the gradients: one row per Gaussian
+    left = DUMP_BUDGET_BYTES - sum(4 * v.numel() for v in images.values())
+    row_bytes = 8 + sum(4 * (v.numel() // P) for v in per_gauss.values())
+    rows = max(0, min(P, left // row_bytes))
+    idx = np.arange(P) if rows == P else np.sort(np.random.default_rng(0).choice(P, rows, replace=False))
+    for k, v in images.items():
+        np.save(os.path.join(path, k + ".npy"), v.float().cpu().numpy())
+    it = torch.from_numpy(idx).to(next(iter(last.values())).device)
+    for k, v in per_gauss.items():
+        np.save(os.path.join(path, k + ".npy"), v.index_select(0, it).float().cpu().numpy())
+    np.save(os.path.join(path, "gaussian_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1198,6 +1243,12 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="collective backend for the barriers (nccl == RCCL)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST MODE: let ranks share GPUs when there are fewer GPUs than ranks (never a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-stage profile and roofline, spread blocks, view-cache and rotation blocks, "
+                         "per-rank figures, scene statistics, the next rows, the parity build, the CPU baselines and the parity check "
+                         "(the --no-* options above select among these); without it a run times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (images, radii, gradients) as float32 DIR/<name>.npy")
     args = ap.parse_args()
 
     from gscream_amd import multi
@@ -1277,19 +1328,22 @@ def main():
         torch.cuda.synchronize()
         warm_extra += 8
     barrier()
-    # Timed region: exactly K steps.  Only the dominant kernel (the backward blend, established by the warm-up
+    # Timed region: exactly K steps.  With --full, only the dominant kernel (the backward blend, established by the warm-up
     # profile below) is bracketed by HIP events here -- timing every stage inserts ~10 event markers per step and
     # measurably stretches the step; the full per-stage profile is taken over K more steps afterwards.
-    _native.profile_begin()
-    for _ in range(3):
-        step()
-    barrier()
-    wprof = _native.profile_end()
-    dom_stage = max(wprof, key=lambda k: wprof[k][0] / max(wprof[k][1], 1))
+    if args.full:
+        _native.profile_begin()
+        for _ in range(3):
+            step()
+        barrier()
+        wprof = _native.profile_end()
+        dom_stage = max(wprof, key=lambda k: wprof[k][0] / max(wprof[k][1], 1))
+    if args.views > 1:  # (the warm-up ran for a time, not a step count: the timed steps start from the same cloud and view in every run)
+        sb.rewind_rotation()
     barrier()
     # (the dominant kernel is bracketed by HIP events in every FOURTH step of the timed region: each pair costs the stream a bubble
     # on either side of the kernel -- with a pair in every step the region ran 2.5 % slower than the same loop without any)
-    if not os.environ.get("GSR_BENCH_NO_BRACKET"):  # (diagnostic knob: what the brackets cost the region)
+    if args.full and not os.environ.get("GSR_BENCH_NO_BRACKET"):  # (diagnostic knob: what the brackets cost the region)
         _native.profile_begin([dom_stage], every=4)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1297,6 +1351,42 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    last = sb.last  # (what the timed path computed in its last step; the --full measurements below run further steps)
+
+    def headline(rate, ms_per_step):
+        """The result line's own fields: what was timed, on what, and how fast."""
+        from gscream_amd import rasterizer as RZ
+        return {
+            "metric": "train iters/sec (fwd+bwd raster) @ 1M Gaussians, 1008x567",
+            "value": round(rate, 3), "unit": "iters/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_extra_steps": warm_extra,
+            "warmup_note": f"the W warm-up steps are followed by further UNTIMED steps of the same workload until the GPU has been busy for {WARM_MS:.0f} ms "
+                           "(GSR_BENCH_WARM_MS): W = 5 steps are 2 ms of work behind seconds of host-side scene construction, and a K = 20 region "
+                           "timed right behind them read 2257-2308 it/s where this reads 2432-2441 (profiles/r05_bench_region.txt)",
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": desc if args.views <= 1 else desc + f" -- NOT BASELINE's line: the timed steps rotate through {args.views} views with perturbed Gaussians (--views)",
+                       "views": args.views, "P": P, "W": W, "H": H, "num_rendered": RZ._last_stage1["num_rendered"],
+                       "tile_cull": not args.no_tile_cull,
+                       "parallelism": f"{world} independent scene(s), one per GPU, barrier only",
+                       "collective_backend": None if dist is None else dist.get_backend(),
+                       "collective_world_size": 1 if dist is None else dist.get_world_size(),
+                       "oversubscribed_test_mode": bool(args.oversubscribe)},
+            **({"fitted_run": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in FIT_INFO.items()}} if FIT_INFO else {}),
+        }
+
+    if not args.full:
+        total_steps, elapsed, rate = multi.aggregate_throughput(dist, args.steps, elapsed, dev)
+        if rank == 0:
+            out = headline(rate, elapsed / args.steps * 1e3)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last, P)
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     dom_prof = _native.profile_end()
     _native.profile_begin()
     for _ in range(args.steps):
@@ -1437,24 +1527,11 @@ def main():
         total_bytes, total_bytes_ref = sum(model.values()), sum(model_ref.values())
         moved_step = sum(pmc.get(k, 0) for k in stages) if pmc and all(k in pmc for k in stages) else None
         valu = valu_roofline(pmc, dom, stages[dom]["avg_ms"])
-        out = {
-            "metric": "train iters/sec (fwd+bwd raster) @ 1M Gaussians, 1008x567",
-            "value": round(rate, 3), "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_extra_steps": warm_extra,
-            "warmup_note": f"the W warm-up steps are followed by further UNTIMED steps of the same workload until the GPU has been busy for {WARM_MS:.0f} ms "
-                           "(GSR_BENCH_WARM_MS): W = 5 steps are 2 ms of work behind seconds of host-side scene construction, and a K = 20 region "
-                           "timed right behind them read 2257-2308 it/s where this reads 2432-2441 (profiles/r05_bench_region.txt)",
-            "ms_per_step": round(ms_per_step, 4),
+        out = headline(rate, ms_per_step)
+        out["config"].update(num_rendered=R, num_rendered_reference=R_ref, visible=visible)
+        out.update({
             "ms_per_step_spread": {"note": "three further blocks of `steps` steps on this rank, timed like the official region (which `value` comes from)",
                                    "blocks_ms": [round(v, 4) for v in spread_ms], "min": round(min(spread_ms), 4), "max": round(max(spread_ms), 4)},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": desc if args.views <= 1 else desc + f" -- NOT BASELINE's line: the timed steps rotate through {args.views} views with perturbed Gaussians (--views)",
-                       "views": args.views, "P": P, "W": W, "H": H, "num_rendered": R, "num_rendered_reference": R_ref,
-                       "visible": visible, "tile_cull": not args.no_tile_cull,
-                       "parallelism": f"{world} independent scene(s), one per GPU, barrier only",
-                       "collective_backend": None if dist is None else dist.get_backend(),
-                       "collective_world_size": 1 if dist is None else dist.get_world_size(),
-                       "oversubscribed_test_mode": bool(args.oversubscribe)},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["survey_model_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(stages[dom]["survey_model_GBps"] / HBM_PEAK_GBS, 4), "traffic": pmc.get(dom), "traffic_source": traffic_source,
                          "algorithmic_bytes_per_launch": model[dom], "avg_launch_ms": stages[dom]["avg_ms"], "valu": valu,
@@ -1482,11 +1559,10 @@ def main():
             "stages": stages,
             "per_rank": per_rank,
             "scene_stats": scene_stats(sb),
-            **({"fitted_run": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in FIT_INFO.items()}} if FIT_INFO else {}),
             "stages_note": "survey_model_* = SURVEY 8(d) per-stage bytes of the REFERENCE algorithm (e.g. six radix passes for tile_sort) over our "
                            "launch time: a work-equivalent rate that can exceed the HBM peak where our kernel moves fewer bytes; pmc_moved_* = bytes "
                            "the launch really moved (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, profiles/pmc_latest.json)",
-        }
+        })
         if world == 1:
             try:
                 ceil = copy_ceiling(dev)
@@ -1531,6 +1607,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["parity_check"], out["cpu_baseline"] = cpu_baseline(P, W, H, multi.scene_seed(seed, rank, world), gsel, args.cpu_budget, args.workload)
             out["cpu_torch_naive"] = cpu_torch_naive()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, P)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

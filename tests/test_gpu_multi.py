@@ -174,7 +174,7 @@ def _bench(*extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "3", "--warmup", "2",
-           "--no-cpu-baseline", "--no-next-rows", *extra]
+           "--full", "--no-cpu-baseline", "--no-next-rows", *extra]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     return p
 

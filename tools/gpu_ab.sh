@@ -16,7 +16,7 @@ import json,sys
 d=json.loads(sys.stdin.read())
 print(sys.argv[1], sys.argv[2], d['value'], d['ms_per_step'], {k:round(v['avg_ms']*1e3,1) for k,v in d.get('stages',{}).items()})" "$1" "$2"; }
 run() { local wl=$1 name=$2; shift 2
-  env "$@" timeout 600 python bench.py --no-cpu-baseline --no-next-rows --no-strict-parity --steps $STEPS --warmup $WARMUP --workload $wl ${BENCH_ARGS:-} 2>>"$OUT/err.log" | tail -1 | row $wl $name | tee -a "$OUT/ab.txt"
+  env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-next-rows --no-strict-parity --steps $STEPS --warmup $WARMUP --workload $wl ${BENCH_ARGS:-} 2>>"$OUT/err.log" | tail -1 | row $wl $name | tee -a "$OUT/ab.txt"
 }
 for wl in $WORKLOADS; do for r in $(seq $REPEAT); do
   run $wl shipped A=1

@@ -11,8 +11,8 @@ cp profiles/pmc_latest.json "$OUT/pmc_latest_before.json" 2>/dev/null
 python tools/pmc_summary.py "$OUT/pmc" $WL > "$OUT/pmc.md" 2>> "$OUT/pmc.log"
 cp profiles/pmc_latest.json "$OUT/pmc_latest.json"
 rm -rf "$OUT/pmc"
-timeout 900 python bench.py --workload $WL 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"
-rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt -- python bench.py --workload $WL --no-cpu-baseline --no-next-rows 2> "$OUT/kt.err" | tail -1 > "$OUT/bench_profiled.json"
+timeout 900 python bench.py --full --workload $WL 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"
+rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt -- python bench.py --full --workload $WL --no-cpu-baseline --no-next-rows 2> "$OUT/kt.err" | tail -1 > "$OUT/bench_profiled.json"
 DB=$(find "$OUT/kt" -name "*_results.db" | head -1)
 python tools/rocprof_summary.py "$DB" > "$OUT/kernel_stats.md" 2>> "$OUT/kt.err"
 rm -rf "$OUT/kt"
