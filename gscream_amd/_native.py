@@ -20,6 +20,7 @@ EXPORTED_SYMBOLS = (
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_decode_count", "gsr_decode_emit", "gsr_decode_backward",
     "gsr_depth_loss_workspace_bytes", "gsr_depth_loss_forward", "gsr_depth_loss_backward", "gsr_training_stats",
     "gsr_decode_weight_grad_workspace_bytes", "gsr_decode_zero_hidden_rows", "gsr_decode_visible_rows", "gsr_adaptive_reset",
+    "gsr_anchor_grow_workspace_bytes", "gsr_anchor_grow_keys", "gsr_anchor_grow_emit", "gsr_scatter_max",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -138,6 +139,14 @@ def load():
     lib.gsr_depth_loss_backward.argtypes = [_c_int, _c_int] + [_vp] * 7
     lib.gsr_training_stats.restype = _c_int
     lib.gsr_training_stats.argtypes = [_c_int, _c_int, _c_int] + [_vp] * 11
+    lib.gsr_anchor_grow_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_anchor_grow_workspace_bytes.argtypes = [_c_int, _c_int]
+    lib.gsr_anchor_grow_keys.restype = _c_int
+    lib.gsr_anchor_grow_keys.argtypes = [_c_int] * 3 + [_vp] * 4 + [_c_float] + [_vp] * 5
+    lib.gsr_anchor_grow_emit.restype = _c_int
+    lib.gsr_anchor_grow_emit.argtypes = [_c_int] * 5 + [_vp] * 4 + [_c_float] + [_vp] * 5
+    lib.gsr_scatter_max.restype = _c_int
+    lib.gsr_scatter_max.argtypes = [_c_int] * 3 + [_vp] * 5
     _lib = lib
     return lib
 

@@ -869,3 +869,53 @@ extern "C" int gsr_training_stats(int Nv, int K, int M, const int32_t* visible, 
     return GSR_OK;
 }
 
+
+// ---- anchor growing (anchor_grow.hip) ----
+extern "C" size_t gsr_anchor_grow_workspace_bytes(int N, int L)
+{
+    if (N < 0 || L < 0) return 0;
+    return gag_workspace_bytes(N, L);
+}
+
+static int gag_check_sizes(const char* what, int N, int K, int L)
+{
+    if (N < 0 || K < 1 || L < 0 || (long long)L > (long long)N * K || L > 0x7fffff00)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes N=%d K=%d L=%d (need 0 <= L <= N*K < 2^31)", what, N, K, L);
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_grow_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling,
+                                    const uint8_t* candidate_mask, float inv_size, void* workspace, int64_t* keys, int32_t* rows,
+                                    int32_t* info, void* stream)
+{
+    if (int rc = gag_check_sizes("anchor grow keys", N, K, L)) return rc;
+    if (!workspace || !info || (N > 0 && !anchor) || (L > 0 && (!offset || !scaling || !candidate_mask || !keys || !rows)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow keys: a required pointer is NULL");
+    GSR_HIP(gag_launch_keys(N, K, L, anchor, offset, scaling, candidate_mask, inv_size, workspace, keys, rows, info, (hipStream_t)stream),
+            "anchor grow keys");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_grow_emit(int N, int K, int F, int L, int M, const float* anchor_feat, const int64_t* sorted_keys,
+                                    const int64_t* order, const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor,
+                                    float* new_feat, int32_t* info, void* stream)
+{
+    if (int rc = gag_check_sizes("anchor grow emit", N, K, L)) return rc;
+    if (F < 0 || M < 0 || M > L) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow emit: bad sizes F=%d M=%d L=%d", F, M, L);
+    if (!workspace || !info || (M > 0 && (!sorted_keys || !order || !rows || !candidate_anchor || (F > 0 && (!anchor_feat || !new_feat)))))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow emit: a required pointer is NULL");
+    GSR_HIP(gag_launch_emit(N, K, F, L, M, anchor_feat, sorted_keys, order, rows, cur_size, workspace, candidate_anchor, new_feat, info,
+                            (hipStream_t)stream),
+            "anchor grow emit");
+    return GSR_OK;
+}
+
+extern "C" int gsr_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, void* stream)
+{
+    if (R < 0 || F < 0 || S < 0 || (long long)R * F > (1ll << 40) || (long long)S * F > (1ll << 40))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: bad sizes R=%d F=%d S=%d", R, F, S);
+    if ((long long)S * F > 0 && (!out || !argmax)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: out / argmax is NULL");
+    if ((long long)R * F > 0 && (long long)S * F > 0 && (!src || !index)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: src / index is NULL");
+    GSR_HIP(gag_launch_scatter_max(R, F, S, src, index, out, argmax, (hipStream_t)stream), "scatter_max");
+    return GSR_OK;
+}

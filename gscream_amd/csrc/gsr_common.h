@@ -417,3 +417,12 @@ hipError_t gst_launch_training_stats(int Nv, int K, int M, const int32_t* visibl
                                      const uint8_t* selection, const uint32_t* first, const uint8_t* update_filter,
                                      const float* viewspace_grad, float* opacity_accum, float* anchor_demon,
                                      float* offset_gradient_accum, float* offset_denom, hipStream_t stream);
+
+// ---- anchor_grow.hip (anchor growing: one level's dedupe + max; torch_scatter.scatter_max) ----
+size_t gag_workspace_bytes(int N, int L);
+hipError_t gag_launch_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling, const uint8_t* mask, float inv,
+                           void* workspace, int64_t* keys, int32_t* rows, int32_t* info, hipStream_t stream);
+hipError_t gag_launch_emit(int N, int K, int F, int L, int M, const float* feat, const int64_t* sorted_keys, const int64_t* perm,
+                           const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor, float* new_feat, int32_t* info,
+                           hipStream_t stream);
+hipError_t gag_launch_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, hipStream_t stream);

@@ -293,6 +293,38 @@ int gsr_training_stats(int Nv, int K, int M, const int32_t* visible, const float
                        void* stream);
 
 /*
+ * Anchor growing, one level (the tensor math of GaussianModel.anchor_growing, scene/gaussian_model.py:834-874): quantise the
+ * candidates all_xyz = anchor + offset * scaling[:, :3] (:829) to cells round(xyz / cur_size) (:840-841), keep one per cell
+ * in ascending (x, y, z) order (torch.unique(dim=0), :843), drop cells an existing anchor occupies (the chunked U x N test
+ * of :846-857, here a hash table of the N anchor cells), write candidate_anchor = cell * cur_size (:863) and new_feat = the
+ * per-channel max of anchor_feat[row / K] over the cell's candidates (scatter_max, :872-874).  Bit-identical, same row order.
+ * Two calls around a STABLE sort of the keys done by the caller:
+ *   gsr_anchor_grow_keys: anchor[N,3], offset[N,K,3], scaling[N,>=3 of 6] (the ACTIVATED scaling, row stride 6),
+ *     candidate_mask[L] (u8, L <= N*K: rows beyond L are not candidates), inv_size = 1.0f / (float)cur_size (PyTorch's GPU
+ *     division by a Python scalar multiplies by this reciprocal).  Writes the 63-bit cell keys[M] (int64, 21 bits per axis
+ *     biased by 2^20) and flat mask rows rows[M] (int32) of the M candidates in mask order, and info[0] = M,
+ *     info[1] = flags: bit 0 a candidate cell outside [-2^20, 2^20) or non-finite, bit 1 a non-finite anchor; with a flag
+ *     set the level must be computed another way (the keys do not represent it).  info: int32[4] on the device.
+ *   gsr_anchor_grow_emit: sorted_keys[M] and order[M] (int64: the stably sorted keys and their positions in keys[]),
+ *     rows[] and the workspace of the keys call, anchor_feat[N,F], cur_size as fp32.  Writes candidate_anchor[C,3],
+ *     new_feat[C,F] (buffers sized M) and info[2] = C.
+ * workspace: gsr_anchor_grow_workspace_bytes(N, L), the same for both calls.
+ */
+size_t gsr_anchor_grow_workspace_bytes(int N, int L);
+int gsr_anchor_grow_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling,
+                         const uint8_t* candidate_mask, float inv_size, void* workspace, int64_t* keys, int32_t* rows,
+                         int32_t* info, void* stream);
+int gsr_anchor_grow_emit(int N, int K, int F, int L, int M, const float* anchor_feat, const int64_t* sorted_keys,
+                         const int64_t* order, const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor,
+                         float* new_feat, int32_t* info, void* stream);
+/*
+ * torch_scatter.scatter_max(src, index, dim=0) for fp32 src[R,F] and a row index index[R] (int64; the broadcast form
+ * gaussian_model.py:874 uses): out[S,F] = per-channel max over the rows r with index[r] = s, argmax[S,F] = the smallest such
+ * r; slots no row reaches hold 0 and argmax R.  Rows whose index is outside [0, S) are ignored.
+ */
+int gsr_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, void* stream);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
