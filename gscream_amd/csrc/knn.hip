@@ -182,22 +182,24 @@ __device__ __forceinline__ void gsk_update3(float dist, float best[3])  // simpl
         if (best[j] > dist) { const float t = best[j]; best[j] = dist; dist = t; }
 }
 
+// x^2 + y^2 + z^2 in ONE fixed rounding sequence, for point distances and box bounds alike.  A prune compares a box bound
+// with a point distance: fp32 rounding is monotonic, so with the same sequence a bound never rounds above the distance of
+// a point in the box.  (With the sums left to contraction, a neighbour on the box corner nearest to the query -- bound and
+// distance equal in exact arithmetic -- was pruned once its box bound came out one ulp above the seed's distance.)
+__device__ __forceinline__ float gsk_len2(float x, float y, float z) { return __fmaf_rn(z, z, __fmaf_rn(y, y, __fmul_rn(x, x))); }
+
 __device__ __forceinline__ float gsk_dist2(const float4 a, const float4 b)
 {
-    const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-    return dx * dx + dy * dy + dz * dz;
+    return gsk_len2(b.x - a.x, b.y - a.y, b.z - a.z);
 }
 
 // squared distance between two axis-aligned boxes (0 if they overlap)
 __device__ __forceinline__ float gsk_box_box(const float lo[3], const float hi[3], const GskBox& b)
 {
-    float d2 = 0.f;
+    float g[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float g = fmaxf(fmaxf(b.lo[k] - hi[k], lo[k] - b.hi[k]), 0.f);
-        d2 += g * g;
-    }
-    return d2;
+    for (int k = 0; k < 3; k++) g[k] = fmaxf(fmaxf(b.lo[k] - hi[k], lo[k] - b.hi[k]), 0.f);
+    return gsk_len2(g[0], g[1], g[2]);
 }
 
 __global__ void __launch_bounds__(GSK_GROUP) gsk_search_kernel(int P, int nboxes, const float4* __restrict__ sp,
@@ -256,15 +258,16 @@ __global__ void __launch_bounds__(GSK_GROUP) gsk_search_kernel(int P, int nboxes
         }
         __syncthreads();
         // the member's own exact test (simple_knn.cu:165-168)
-        float d2 = 0.f;
+        float d2;
         {
             const float p[3] = { me.x, me.y, me.z };
+            float g[3];
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                float g = 0.f;
-                if (p[k] < box.lo[k] || p[k] > box.hi[k]) g = fminf(fabsf(p[k] - box.lo[k]), fabsf(p[k] - box.hi[k]));
-                d2 += g * g;
+                g[k] = 0.f;
+                if (p[k] < box.lo[k] || p[k] > box.hi[k]) g[k] = fminf(fabsf(p[k] - box.lo[k]), fabsf(p[k] - box.hi[k]));
             }
+            d2 = gsk_len2(g[0], g[1], g[2]);
         }
         if (!live || d2 > reject || d2 > best[2]) continue;
         const int n = min(GSK_BOX, P - b * GSK_BOX);

@@ -405,3 +405,75 @@ def assert_parity_strict(got, st, ref=None, s=None, grads=None, context="", keys
         print(f"[classified] {context}: {ties} expf-tie pixel(s): {[p_ for p_ in rep['outlier_pixels'] if p_['expf_tie']]}")
     return rep
 
+
+
+# ---- compacted decode rows at training sizes -------------------------------------------------------------------------
+# The decode keeps offset k of anchor n (key n*K + k) when tanh(z) > 0.  With millions of keys, some z sits within fp32
+# rounding of zero and the kernel and the fp64 oracle may keep different sets; a seed search for a clean mask does not
+# scale.  Instead both sides' output rows are mapped back to their keys and compared on the keys both kept, and the
+# upstream gradient is one field over the keys, zero where the masks differ, gathered by each side through its own mask.
+def align_decode_rows(mask_got, mask_ref, nop_ref, sure=1e-5):
+    """mask_got / mask_ref: the two selection masks [Nv*K]; nop_ref: the reference's neural_opacity (same keys).
+    Asserts that the masks agree wherever |nop_ref| > `sure`.  Returns a namespace with
+      keys_got / keys_ref : the key of every output row of each side (its mask's nonzero positions, in row order)
+      rows_got / rows_ref : for every key both sides kept, its output row on either side (ascending key order)
+      ambiguous           : bool [Nv*K], the keys where the masks differ
+    """
+    import types
+    import torch
+    mg = mask_got.detach().cpu().view(-1).bool()
+    mr = mask_ref.detach().cpu().view(-1).bool()
+    assert mg.shape == mr.shape, (mg.shape, mr.shape)
+    diff = mg != mr
+    near_zero = nop_ref.detach().cpu().view(-1).abs() <= sure
+    assert not bool((diff & ~near_zero).any()), f"mask differs away from zero at keys {torch.nonzero(diff & ~near_zero).view(-1)[:8].tolist()}"
+    row_g = torch.cumsum(mg.long(), 0) - 1  # output row of key i on either side (valid where the mask keeps i)
+    row_r = torch.cumsum(mr.long(), 0) - 1
+    both = torch.nonzero(mg & mr).view(-1)
+    return types.SimpleNamespace(keys_got=torch.nonzero(mg).view(-1), keys_ref=torch.nonzero(mr).view(-1),
+                                 rows_got=row_g[both], rows_ref=row_r[both], ambiguous=diff)
+
+
+def upstream_fields(nkeys, widths, ambiguous, generator, mean=0.0, dtype=None):
+    """One random upstream-gradient field [nkeys, w] per output width (N(mean, 1) entries), zero on the ambiguous keys."""
+    import torch
+    out = []
+    for w in widths:
+        f = torch.randn((nkeys, w), generator=generator, dtype=dtype or torch.float64) + mean
+        f[ambiguous] = 0.0
+        out.append(f)
+    return out
+
+
+def max_scaled_err(a, b):
+    """max |a - b| / max(1, max |b|): the measure of the decode tests' `_close`."""
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    assert a.shape == b.shape, (a.shape, b.shape)
+    if not a.numel():
+        return 0.0
+    return (a - b).abs().max().item() / max(1.0, b.abs().max().item())
+
+
+def morton_bucket_counts(pts, bits=12):
+    """Occupancy of the kNN kernel's Morton buckets (knn.hip gsk_morton_kernel): the cloud's bounding box (its reduction
+    starts from the origin), 10-bit cells per axis in fp32, x | y << 1 | z << 2 interleaved, bucket = the top `bits` of the
+    30-bit code."""
+    p = np.asarray(pts, dtype=np.float32)
+    lo = np.minimum(p.min(0), np.float32(0)).astype(np.float32)
+    hi = np.maximum(p.max(0), np.float32(0)).astype(np.float32)
+    q = (((p - lo) / (hi - lo)) * np.float32(1023)).astype(np.uint32)
+    code = np.zeros(p.shape[0], np.uint32)
+    for b in range(10):
+        for k in range(3):
+            code |= ((q[:, k] >> np.uint32(b)) & np.uint32(1)) << np.uint32(3 * b + k)
+    return np.bincount(code >> np.uint32(30 - bits), minlength=1 << bits)
+
+
+def record_first_layers(model, names=("mlp_opacity", "mlp_uncertainty", "mlp_color", "mlp_cov")):
+    """Forward hooks on the first Linear layer of the decode's four MLPs: -> (list that collects their outputs, the ReLU
+    inputs [n, 32] of every decoded anchor, in call order; a function that removes the hooks).  A ReLU input within fp32
+    rounding of zero flips the unit's derivative between an fp32 kernel and the fp64 oracle: the anchor's input gradient
+    then differs by a whole weight column, as CPU fp32 torch on the same expressions shows.  (Cloned: the ReLU runs in place.)"""
+    seen = []
+    hooks = [getattr(model, n)[0].register_forward_hook(lambda _m, _i, o: seen.append(o.detach().clone())) for n in names]
+    return seen, lambda: [h.remove() for h in hooks]

@@ -194,10 +194,11 @@ def test_training_statistics_against_oracle():
     assert acc_d.anchor_demon.max() == 2 and acc_d.offset_denom.sum() > 0
 
 
-@pytest.mark.parametrize("N", [0, 1, 63, 255, 256, 257, 1000, 200_001])
+@pytest.mark.parametrize("N", [0, 1, 63, 255, 256, 257, 1000, 200_001, 262_144, 262_145, 600_000])
 def test_visible_rows_on_the_device_match_nonzero(N):
     """gsr_decode_visible_rows (the row list of the visible anchors without torch.nonzero's host round trip): same rows, same
-    order, same count as torch.nonzero, for sizes around the block edges."""
+    order, same count as torch.nonzero, for sizes around the block edges and past 1024 x 256 rows (the scan's threads then own
+    several block totals each)."""
     from gscream_amd import _native
     lib = _native.load()
     dev = torch.device("cuda", 0)
