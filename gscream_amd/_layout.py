@@ -3,14 +3,12 @@ decodes the opaque geom / image / binning byte tensors the forward returns."""
 import torch
 
 
-import os
-
-# GSR_SEG1, GSR_T2_LEN, GSR_T2_N, GSR_SEG3_LEN, GSR_SEG2 (gsr_common.h): three tiers of depth segments at fixed list positions
-# (the env knobs: A/B against a library built with other -D values)
-SEG1 = 7
-T2_LEN, T2_N = int(os.environ.get("GSR_T2_LEN", "3")), int(os.environ.get("GSR_T2_N", "6"))
-SEG3_LEN = int(os.environ.get("GSR_SEG3_LEN", "8"))
-SEG2 = int(os.environ.get("GSR_SEG2", "20"))
+# three tiers of depth segments at fixed list positions (gsr_common.h; plain #defines there, literals here)
+SEG1 = 7        # GSR_SEG1
+T2_LEN = 3      # GSR_T2_LEN
+T2_N = 6        # GSR_T2_N
+SEG3_LEN = 8    # GSR_SEG3_LEN
+SEG2 = 20       # GSR_SEG2
 SEG_MAX = SEG1 + SEG2    # GSR_SEG_MAX: segments per tile = checkpoint slots (SEG_MAX - 1 checkpoints + the "last" slot)
 CKPT_PLANES = SEG_MAX * 6
 # ends of the segments behind the first tier in units of L
@@ -18,13 +16,14 @@ SEG2_ENDS = tuple(SEG1 + T2_LEN * (j + 1) for j in range(T2_N)) + tuple(SEG1 + T
 
 
 def seg2_len(n, L):
-    """gsr_seg2_len: the unit of the second tier's boundaries = the launch's segment length L (64 up to 4096 tiles, 128 beyond),
+    """The unit of the boundaries behind the first tier = the launch's segment length L (64 up to 4096 tiles, 128 beyond),
     whatever the list length n."""
     return L
 
 
 def ckpt_pos(k, L, unit):
-    """gsr_ckpt_pos: list position of checkpoint k = 0 .. SEG_MAX-2 (fixed positions: they do not depend on the list)."""
+    """gsr_ckpt_pos: list position of checkpoint k = 0 .. SEG_MAX-2 (fixed positions: they do not depend on the list).
+    `unit` is always L."""
     return (k + 1) * L if k < SEG1 else unit * SEG2_ENDS[k - SEG1]
 
 
@@ -32,7 +31,7 @@ def _align(x):
     return (x + 255) & ~255
 
 
-MAX_CHUNKS, CHUNK_GAUSS = 256, 1024  # GSR_MAX_CHUNKS, GSR_CHUNK_GAUSS (gsr_common.h)
+MAX_CHUNKS, CHUNK_GAUSS, MAX_TILES_LDS = 256, 1024, 36864  # GSR_MAX_CHUNKS, GSR_CHUNK_GAUSS, GSR_MAX_TILES_LDS (gsr_common.h)
 
 
 def num_chunks(P):
@@ -56,9 +55,7 @@ def geom_views(buf, P):
     return {k: v[:P] for k, v in out.items()}
 
 
-OCC_BUCKETS = 160
-
-
+OCC_BUCKETS, OCC_MAX_TILES, OCC_COPIES = 160, 8192, 8   # GSR_OCC_BUCKETS, GSR_OCC_MAX_TILES, GSR_OCC_COPIES (gsr_common.h)
 XCD_CHUNK = 4   # gsr_common.h GSR_XCD_CHUNK: consecutive tiles an XCD gets at a time
 
 
@@ -81,14 +78,14 @@ def image_views(buf, P, W, H):
     out["ranges"] = _take(buf, off, T * 8, torch.int32, (T, 2)); off += _align(T * 8)
     out["final_T"] = _take(buf, off, N * 4, torch.float32, (H, W)); off += _align(N * 4)
     out["n_contrib"] = _take(buf, off, N * 4, torch.int32, (H, W)); off += _align(N * 4)
-    nb = num_chunks(P) if T <= 36864 else 1  # beyond the LDS tile limit only T cursor words (gsr_common.h)
+    nb = num_chunks(P) if T <= MAX_TILES_LDS else 1  # beyond the LDS tile limit only T cursor words (gsr_common.h)
     out["table"] = _take(buf, off, nb * T * 4, torch.int32, (nb, T)); off += _align(nb * T * 4)
     out["tile_count"] = _take(buf, off, T * 4, torch.int32, (T,)); off += _align(T * 4)
     out["tile_work"] = _take(buf, off, T * 4, torch.int32, (T,)); off += _align(T * 4)
     out["sorted_len"] = _take(buf, off, T * 4, torch.int32, (T,)); off += _align(T * 4)
     out["need_full"] = _take(buf, off, T * 4, torch.int32, (T,)); off += _align(T * 4)
     Np = (N + 3) & ~3
-    nocc = 8 * T * OCC_BUCKETS if T <= 8192 else 1   # occlusion cut-off: occ_mass x 8 XCD copies ALIASES the checkpoint area (gsr_common.h)
+    nocc = OCC_COPIES * T * OCC_BUCKETS if T <= OCC_MAX_TILES else 1   # occlusion cut-off: occ_mass, one copy per XCD, ALIASES the checkpoint area (gsr_common.h)
     out["ckpt"] = _take(buf, off, CKPT_PLANES * Np * 4, torch.float32, (SEG_MAX, 6 * Np))
     out["occ_mass"] = _take(buf, off, nocc * 4, torch.int32, (nocc,))
     off += _align(max(CKPT_PLANES * Np * 4, nocc * 4))
@@ -97,7 +94,7 @@ def image_views(buf, P, W, H):
     nq = 32 * xcd_tiles(T)   # dispatch order of the forward's quadrant tasks (gsr_tuning.walk_depths)
     out["qorder"] = _take(buf, off, nq * 4, torch.int32, (8, nq // 8)); off += _align(nq * 4)
     out["occ_cut"] = _take(buf, off, T * 4, torch.int32, (T,)); off += _align(T * 4)
-    out["occ_drop"] = _take(buf, off, 256 * 4, torch.int32, (256,)); off += _align(256 * 4)
+    out["occ_drop"] = _take(buf, off, MAX_CHUNKS * 4, torch.int32, (MAX_CHUNKS,)); off += _align(MAX_CHUNKS * 4)
     out["tile_group"] = _take(buf, off, (T // 64 + 1) * 4, torch.int32, (T // 64 + 1,)); off += _align((T // 64 + 1) * 4)
     return out
 

@@ -539,14 +539,10 @@ __global__ void __launch_bounds__(GSR_HIST_THREADS) gsr_scatter_kernel(
             }
             gsr_wave_for_each_instance(rcb, mkb, dks[k], heads, [&](int owner, int x, int y, uint32_t odk) {
                 const uint32_t slot = atomicAdd(&cursor[y * gx + x - t_lo], 1u);
-#ifdef GSR_SCATTER_NOSTORE  // diagnostic: everything but the key stores (are the 32-byte-sector writes what the kernel waits for?)
-                if (slot == 0xffffffffu) seg_keys[0] = odk;
-#else
                 const u64 key = ((u64)odk << 32) | (uint32_t)(g_lane0 + owner);
                 if (staged) {
                     if (slot < stage_cap) { skey[slot] = key; stile[slot] = (uint16_t)(y * gx + x - t_lo); }  // (always true: the counts are exact)
                 } else if (slot < capacity) seg_keys[slot] = key;  // capacity < R only in a speculative launch that is redone
-#endif
             });
         }
     }
@@ -1129,9 +1125,6 @@ hipError_t gsr_launch_scatter(int P, int T, int gx, const GsrGeom& geom, const G
         if (want < stage_cap) stage_cap = want;
     }
     stage_cap &= ~(size_t)63;
-#ifdef GSR_SCATTER_NO_STAGING
-    stage_cap = 0;
-#endif
     const size_t lds = stage_cap ? fixed + stage_cap * 10 : tb * 4;
     if (nbands > 1)
         hipLaunchKernelGGL((gsr_scatter_kernel<false, true>), dim3(nchunks * nbands), dim3(GSR_HIST_THREADS), lds, stream, P, T, gx, nchunks,

@@ -13,9 +13,9 @@
 //   * Backward: one 128-thread workgroup per DEPTH SEGMENT of a tile (see gsr_blend_bwd_kernel): the forward stores,
 //     per pixel and every 64 / 128 list positions, the transmittance and the sums of the segment that ends there, so a
 //     segment can be walked back to front without the ones behind it.  Wavefront w owns the 16x8 strip w of the tile,
-//     lane l two pixels of it; the per-pixel arithmetic runs on float2 (v_pk_*).  Thread i gathers the record of
-//     instance i into LDS and computes the 4-bit quadrant mask once per instance; each wave compacts, with ballot +
-//     mbcnt, the indices of the instances that can reach ITS strip into a private LDS list and walks only those.
+//     lane l two pixels of it; the per-pixel arithmetic runs on float2 (v_pk_*).  The two waves gather the records of a
+//     batch of 64 instances into LDS, one half of each record per wave; each wave then tests every instance against ITS
+//     strip and compacts, with ballot + mbcnt, the indices of those that can reach it into a private LDS list and walks only those.
 //     Operands come back with same-address (broadcast) ds_read_b128, software-pipelined one instance ahead; the list
 //     index comes from a per-lane copy via v_readlane (no dependent LDS read).
 //   * Early-out: a forward wave stops when all its pixels are saturated; a backward wave skips gradient math +
@@ -111,7 +111,6 @@ __device__ __forceinline__ GsrExactAlpha gsr_alpha_exact(const float cA, const f
     r.alpha = fminf(0.99f, raw);
     r.blends = !(power > 0.0f) && !(r.alpha < 1.0f / 255.0f);
     r.one_minus = 1.0f - r.alpha;
-    // (twice the guard band's width: the backward decides band membership on the FAST alpha, a few 1e-7 away from this one)
     // (twice the guard band's width: the backward decides band membership on the FAST alpha, a few 1e-7 away from this one)
     r.in_band = !(power > 0.0f) && fabsf(raw - GSR_ALPHA_C) < GSR_ALPHA_C * (2.0f * GSR_BAND);
     return r;
@@ -241,25 +240,6 @@ __device__ __forceinline__ void gsr_bank_reduce_dyf(float c0, float c1, float c2
 // dependent LDS read) and the operands of instance k+1 are in flight while instance k is computed (measured winner
 // against the plain loop, profiles/).
 
-// 4-bit mask of the 8x8 quadrants of tile (tx, ty) in which the Gaussian can reach alpha >= 1/255.
-__device__ __forceinline__ uint32_t gsr_quadrant_mask(const float4 A, const float4 B, const float tau, int tx, int ty,
-                                                      int W, int H)
-{
-    // q2 = log2(e) q = 0.5 (a dx^2 + c dy^2) + b dx dy with (a, b, c) = log2(e) conic; the threshold scales the same way
-    const float ca = GSR_QSCALE(A.z), cb = GSR_QSCALE(A.w), cc = GSR_QSCALE(B.x);  // A, B: the record's raw conic
-    const float rA = GSR_RCP(ca), rC = GSR_RCP(cc);
-    uint32_t m = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int x0 = tx * 16 + (q & 1) * 8, y0 = ty * 16 + (q >> 1) * 8;
-        const float bx1 = (float)min(x0 + 7, W - 1), by1 = (float)min(y0 + 7, H - 1);
-        const bool hit = x0 < W && y0 < H &&
-                         !(gsr_box_min_q(A.x, A.y, ca, cb, cc, rA, rC, (float)x0, bx1, (float)y0, by1) > tau);
-        m |= hit ? (1u << q) : 0u;
-    }
-    return m;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Forward, one independent wavefront per 8x8 quadrant, two instances per loop iteration.
 //
@@ -280,20 +260,13 @@ __device__ __forceinline__ uint32_t gsr_quadrant_mask(const float4 A, const floa
 // reference does; where it blends an instance the reference would have stopped at, its T ends below 1e-4 (1 + band) -- so ONE
 // compare at the end of the walk (final T < 1e-4 (1 + band)) finds every pixel whose stop could differ, at no cost inside the loop
 // (a per-blend test of the stopping test_T cost the launch 5 %).
-#if !defined(GSR_PRECISE_MATH) && !defined(GSR_NO_TREPLAY)
+#ifndef GSR_PRECISE_MATH
 #define GSR_T_STOP (0.0001f * (1.0f - GSR_TBAND))
 #else
 #define GSR_T_STOP 0.0001f
 #endif
-// Dynamic LDS requested (and never touched) per forward workgroup: it caps how many quadrant waves are resident per CU, so
-// that the rest of the 4T workgroups are handed out as earlier ones finish (the dispatcher then balances the SIMDs; with
-// every wave resident from the start a launch lasts as long as its most loaded SIMD).  Compile-time experiment knob
-// (make variant FLAGS=-DGSR_FWD_LDS_PAD=...; measured: every non-zero value is slower); the shipped library
-// reads no environment variable.
-#ifndef GSR_FWD_LDS_PAD
-#define GSR_FWD_LDS_PAD 0
-#endif
-static_assert(GSR_FWD_LDS_PAD >= 0 && GSR_FWD_LDS_PAD <= 60 * 1024, "GSR_FWD_LDS_PAD out of range");
+// (Padding the forward workgroups with untouched dynamic LDS to cap how many quadrant waves are resident per CU was measured: every
+// non-zero value is slower)
 typedef float gsr_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ gsr_f2 gsr_splat(float v) { gsr_f2 r = {v, v}; return r; }
 __device__ __forceinline__ gsr_f2 gsr_fma2(gsr_f2 a, gsr_f2 b, gsr_f2 c) { return __builtin_elementwise_fma(a, b, c); }
@@ -306,14 +279,14 @@ __device__ __forceinline__ float2* gsr_ckpt_b(float* ckpt, int k, size_t HW) { r
 __device__ __forceinline__ const float4* gsr_ckpt_a(const float* ckpt, int k, size_t HW) { return reinterpret_cast<const float4*>(ckpt + (size_t)k * 6 * gsr_ckpt_stride(HW)); }
 __device__ __forceinline__ const float2* gsr_ckpt_b(const float* ckpt, int k, size_t HW) { return reinterpret_cast<const float2*>(ckpt + ((size_t)k * 6 + 4) * gsr_ckpt_stride(HW)); }
 
+#ifndef GSR_DEEP_FLAG_AT
+#define GSR_DEEP_FLAG_AT (GSR_SEG1 + 4)  // checkpoints passed when a walk counts as deep for the backward's launch order: position gsr_ckpt_pos(10) = 19 L
+#endif
 // Waves per SIMD the forward's register allocation is held to.  Round 6: 7 (72 VGPRs + one 8-byte spill that is reloaded once per
 // 64-instance batch) instead of the 74 registers = 6 waves the allocator settles on by itself: 7 168 instead of 6 144 resident quadrant
 // waves of the launch's ~9 000 -- fewer late starters.  Same-box A/B (profiles/r06_waves_per_simd_ab.txt), forward blend us: config 2 without
 // the per-view order 104.5 -> 100.2, with it 93.5 -> 93.2; config 4 207 -> 200; init-state 277 -> 268-276; 8 waves (64 VGPRs, 40 B of
 // scratch) loses everywhere.  0 = no constraint.
-#ifndef GSR_DEEP_FLAG_AT
-#define GSR_DEEP_FLAG_AT (GSR_SEG1 + 4)  // checkpoints passed when a walk counts as deep for the backward's launch order: position gsr_ckpt_pos(10) = 19 L
-#endif
 #ifndef GSR_FWD_WAVES
 #define GSR_FWD_WAVES 7
 #endif
@@ -377,7 +350,6 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
     // are in depth order only up to sorted_len[tile] (binning.hip): the walk ends there, and if a pixel is still
     // blending the tile is flagged and redone after a full sort.
     const int nlist = (int)(rg.y - rg.x), nsort = (int)sorted_len[tile];
-    const int seg2_len = gsr_seg2_len(nlist, seg_len);  // unit of the second tier's (fixed) boundaries (gsr_common.h)
     const int n = (rg.y > capacity || (nsort == nlist && (uint32_t)nlist > longest_sorted)) ? 0 : min(nlist, nsort);
     const bool inside = px < W && py < H;
     const uint32_t HW = (uint32_t)H * (uint32_t)W, pid = inside ? (uint32_t)py * (uint32_t)W + (uint32_t)px : 0u;  // <= 2^24 tiles (api.hip) = at most 2^32 pixels
@@ -469,7 +441,7 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
         // backward needs the sum BEHIND a position to a relative accuracy that final - prefix cannot give once T is
         // small: sums of small terms have to stay small.)
         // (positions are multiples of 64 and batches end at multiples of 64: a checkpoint is always the start of a batch)
-        if (npass < GSR_SEG_MAX - 1 && base == gsr_ckpt_pos(npass, seg_len, seg2_len)) {
+        if (npass < GSR_SEG_MAX - 1 && base == gsr_ckpt_pos(npass, seg_len, seg_len)) {
             if (TRAIN && inside) {  // (inference: the same restarts, so that the sums associate identically, but nothing is stored)
                 gsr_ckpt_a(ckpt, npass, HW)[pid] = make_float4(Tr, C0, C1, C2);
                 gsr_ckpt_b(ckpt, npass, HW)[pid] = make_float2(Dp, Uf);
@@ -553,11 +525,7 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
             // (|alpha - 1/255| of both instances -> one minimum -> ONE compare whose result is branched on directly: the test adds
             // three VALU instructions and no scalar logic to the chain in front of the blends)
             const gsr_f2 dband = al - gsr_splat(GSR_ALPHA_C);
-#ifdef GSR_NO_BAND  // diagnostic: the band test compiled out (what the check costs)
-            if (false) {
-#else
             if (__builtin_amdgcn_ballot_w64(fminf(fabsf(dband.x), fabsf(dband.y)) < GSR_ALPHA_C * GSR_BAND) != 0ull) {  // rare: inside the guard band
-#endif
                 const unsigned long long banda = __builtin_amdgcn_ballot_w64(al.x < GSR_ALPHA_HI) & cma;
                 const unsigned long long bandb = __builtin_amdgcn_ballot_w64(al.y < GSR_ALPHA_HI) & cmb;
                 // -> the reference's own expression decides
@@ -601,21 +569,11 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
                 const unsigned long long stopm = __builtin_amdgcn_ballot_w64(test_T < GSR_T_STOP) & okm;
                 donem |= stopm;
                 const unsigned long long okf = okm & ~stopm;
-#ifdef GSR_FWD_EXEC_MASK
-                if (__builtin_amdgcn_inverse_ballot_w64(okf)) {  // EXEC = the pixels that blend: no selects
-                    const float w = al1 * Tr;
-                    C0 += C.x * w; C1 += C.y * w; C2 += C.z * w;
-                    Dp += C.w * w; Uf += feat * w;
-                    Tr = test_T;
-                    last = (uint32_t)(base + j + 1);
-                }
-#else
                 const float w = gsr_sel0(okf, al1 * Tr);
                 C0 += C.x * w; C1 += C.y * w; C2 += C.z * w;
                 Dp += C.w * w; Uf += feat * w;
                 Tr = gsr_sel(okf, test_T, Tr);
                 last = __float_as_uint(gsr_sel(okf, __uint_as_float((uint32_t)(base + j + 1)), __uint_as_float(last)));
-#endif
             };
             const unsigned long long okma = cma & ~donem;
             GSR_COUNT_ADD(4, 1);                                 // forward: pair iterations
@@ -636,7 +594,7 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
     const bool ran_off = nsort < nlist && rg.y <= capacity && donem != full;
 
     int npl = npass;  // checkpoints passed, per lane: a replayed pixel's own walk may end in another segment than the wave's
-#if !defined(GSR_PRECISE_MATH) && !defined(GSR_NO_TREPLAY)
+#ifndef GSR_PRECISE_MATH
     // ---- exact replay of the pixels near the T = 1e-4 stop (see GSR_TBAND, GSR_T_STOP) ----
     // final T inside the band around 1e-4 (it can lie BELOW 1e-4: the fast walk stops late rather than early): the last blend passed
     // the reference's stop test by less than the band, or failed it by less
@@ -678,7 +636,7 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
                 const RecRegs rc_nxt = fetch_rec(gid_nxt);
                 float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (gid_cur != 0xffffffffu) col = rec[gid_cur].c;
-                if (np2 < GSR_SEG_MAX - 1 && b0 == gsr_ckpt_pos(np2, seg_len, seg2_len)) {  // same restarts as the walk above
+                if (np2 < GSR_SEG_MAX - 1 && b0 == gsr_ckpt_pos(np2, seg_len, seg_len)) {  // same restarts as the walk above
                     // (staged, not stored: a replay that is dropped below must leave the pixel's checkpoints as the fast walk wrote
                     // them -- they belong to the final T / sums the pixel then keeps)
                     if (TRAIN && lane == 0) {
@@ -798,8 +756,9 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
 // ---------------------------------------------------------------------------------------------
 // Backward
 //
-// Work unit = one DEPTH SEGMENT of one tile: GSR_SEG_LEN consecutive list positions (the last segment of a tile takes
-// everything behind (GSR_SEG_MAX-1) * GSR_SEG_LEN).  The reference walks a tile's list back to front carrying
+// Work unit = one DEPTH SEGMENT of one tile: the list positions between two of the forward's checkpoints (gsr_ckpt_pos, gsr_common.h:
+// 64 / 128 positions in the first tier, 3 and 8 times that behind it; the grid's last segment takes everything that is left), staged
+// GSR_BWB instances at a time.  The reference walks a tile's list back to front carrying
 // T and the colour accumulated behind the current instance (backward.cu:500-566); both are functions of the forward's
 // prefix sums, T_e and (C_final - C_front(e)) / T_e, which the forward stores per pixel at the segment boundaries, so
 // every segment can start on its own.  On the bench scene that turns 2268 tile-sized work units (1.8 per wavefront
@@ -812,23 +771,7 @@ __global__ void __launch_bounds__(64) GSR_FWD_ATTR gsr_blend_fwd_kernel(
 // downstream is then exact: T / (1 - 0) = T, 0 * C + 1 * acc = acc, weights 0), and the wave reduction -- the
 // largest fixed cost per (wave, instance) -- is paid once per 128 pixels instead of once per 64.
 // ---------------------------------------------------------------------------------------------
-// Wave-private compaction: indices i < cnt whose quadrant mask sQ[i] meets `qmask` and pred(i), in ascending order.
-template <int SL, typename Pred>
-__device__ __forceinline__ int gsr_compact2(const uint32_t* sQ, uint16_t* list, int cnt, uint32_t qmask, int lane, Pred pred)
-{
-    int n = 0;
-#pragma unroll
-    for (int c = 0; c < SL / 64; c++) {
-        const int i = c * 64 + lane;
-        const bool hit = i < cnt && (sQ[i] & qmask) && pred(i);
-        const unsigned long long bal = __ballot(hit);
-        if (hit) list[n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint16_t)i;
-        n += __popcll(bal);
-    }
-    return n;
-}
-
-// Waves per SIMD of the backward (64-entry form).  Round 6: 6 (80 VGPRs; the RGB-only variant without a spill, the AUX variant with four
+// Waves per SIMD of the backward.  Round 6: 6 (80 VGPRs; the RGB-only variant without a spill, the AUX variant with four
 // dwords spilled in its prologue) instead of 5 (90 / 98 VGPRs): the kernel is VALU-issue-bound at ~77 % of the issue slots, and a sixth
 // wave per SIMD fills some of the rest -- backward blend us, same box: config 2 152 -> 147-150, config 3 172 -> 168.5, config 4 386 ->
 // 372-378, init-state 343 -> 332, `surfaces` 158 -> 153 (profiles/r06_waves_per_simd_ab.txt).  7 (72 VGPRs, 24 / 52 B of scratch): config 2
@@ -836,10 +779,9 @@ __device__ __forceinline__ int gsr_compact2(const uint32_t* sQ, uint16_t* list, 
 #ifndef GSR_BWD_WAVES
 #define GSR_BWD_WAVES 6
 #endif
-// SL = the launch's segment length (64 up to 4096 tiles, 128 beyond): sizes the LDS arrays.
-template <bool AUX, int SL>
-// (the 128-entry form is held to 4 waves per SIMD by its 19.5 KB of LDS per workgroup: its register budget says so too)
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 64 ? GSR_BWD_WAVES : 4, SL == 64 ? GSR_BWD_WAVES : 4))) gsr_blend_bwd_kernel(
+#define GSR_BWB 64  // instances staged per batch: sizes the LDS arrays (the segment, i.e. the checkpoint spacing seg_len, may be longer)
+template <bool AUX>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVES, GSR_BWD_WAVES))) gsr_blend_bwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const GsrRec* __restrict__ rec, int W,
     int H, int gx, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ ckpt, const float* __restrict__ dL_dcolor,
@@ -851,14 +793,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 
     // the per-Gaussian backward that follows appends its heavy groups to a list: this launch, which always precedes it, resets
     // the counter (gauss_bwd.hip)
     if (blockIdx.x == 0 && threadIdx.x == 0) { heavy_groups[0] = 0u; heavy_groups[1] = 0u; }
-    static_assert(SL == 64 || SL == GSR_SEG_LEN, "segment lengths of gsr_seg_len()");
-    __shared__ float4 sA[SL], sB[SL], sC[SL];
+    __shared__ float4 sA[GSR_BWB], sB[GSR_BWB], sC[GSR_BWB];
     // one accumulator array PER WAVEFRONT: a wave's LDS adds are program-ordered and nobody else touches its copy, the flush
     // adds the two copies in a fixed order -> the backward is bit-reproducible (it was not while both waves added into one
     // array in whatever order they arrived)
-    __shared__ __attribute__((aligned(16))) float acc[2][SL * GSR_SLOT_FLOATS];
-    __shared__ uint32_t sSlot[SL], sQ[SL];
-    __shared__ uint16_t sList[2][SL];
+    __shared__ __attribute__((aligned(16))) float acc[2][GSR_BWB * GSR_SLOT_FLOATS];
+    __shared__ uint32_t sSlot[GSR_BWB];
+    __shared__ uint16_t sList[2][GSR_BWB];
 
     GSR_TRACE_BEGIN
 #ifdef GSR_TRACE
@@ -878,33 +819,21 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 
     const int rank = slot / xcd_tiles, tile = gsr_xcd_tile(band, slot - rank * xcd_tiles, T);
     if (rank >= nseg || tile < 0) return;
     const int nbig = nseg - GSR_SEG1;  // segments behind the first tier
-#ifdef GSR_BWD_BIG_FIRST  // (A/B knob: force one order)
-    const bool big_first = GSR_BWD_BIG_FIRST;
-#else
     const uint32_t dw = *deep_walks;  // (wave-uniform scalar load) low bits: quadrant walks that entered the second tier; top bit: one went past 19 L
     const bool big_first = (dw >> 31) != 0u || (dw & 0x7fffffffu) * 4u >= (uint32_t)T;
-#endif
-#ifdef GSR_BWD_TIER2_ASCENDING  // (A/B knob: second-tier segments in list order instead of longest first)
-    const int seg = big_first ? (rank < nbig ? GSR_SEG1 + rank : rank - nbig) : rank;
-#else
     // (the second tier's segments grow with depth: the deepest -- longest -- one first)
     const int seg = big_first ? (rank < nbig ? nseg - 1 - rank : rank - nbig) : rank;
-#endif
     const int tx = tile % gx, ty = tile / gx;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint2 rg = ranges[tile];
     // Instances behind the tile's deepest contributor were blended by no pixel: they are not traversed and their
     // gradient slots are NOT written; slot_written[] (zeroed per call) tells the per-Gaussian kernel which slots exist.
     const int nproc = min((int)(rg.y - rg.x), (int)tile_work[tile]);
-    const int seg2_len = gsr_seg2_len((int)(rg.y - rg.x), seg_len);  // unit of the second tier's (fixed) boundaries, as in the forward
-    const int seg_lo = seg == 0 ? 0 : gsr_ckpt_pos(seg - 1, seg_len, seg2_len);
+    const int seg_lo = seg == 0 ? 0 : gsr_ckpt_pos(seg - 1, seg_len, seg_len);
     // (the grid's last segment takes everything that is left: with the forward's own longest list as the grid's measure that is what its end
     // is anyway; with a SMALLER figure from the caller the lists beyond it are still traversed completely, just by one longer task)
-    const int seg_hi = seg == nseg - 1 ? nproc : min(nproc, gsr_ckpt_pos(seg, seg_len, seg2_len));
+    const int seg_hi = seg == nseg - 1 ? nproc : min(nproc, gsr_ckpt_pos(seg, seg_len, seg_len));
     if (seg_hi <= seg_lo) return;
-#if defined(GSR_BWD_DIAG) && GSR_BWD_DIAG == 1  // diagnostic: dispatch + task lookup only
-    return;
-#endif
 
     // lanes l, l+4, l+8, l+12 of a DPP row share their pixel row (see gsr_bank_reduce_dyf)
     const int pxa = tx * 16 + ((lane >> 1) & 7), pxb = pxa + 8;
@@ -997,17 +926,12 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 
         }
     }
 
-#if defined(GSR_BWD_DIAG) && GSR_BWD_DIAG == 2  // diagnostic: ... + the pixel prologue (final T, gradients, checkpoint sums)
-    if (Tr.x + Ar.x + Tr.y + Ar.y + g0.x + g1.x + g2.x == 12345.678f) slots[0] = make_float4(Tr.x, Ar.x, Tr.y, Ar.y);
-    return;
-#endif
     // wave-level maximum of the last contributor: nothing at a position >= it is blended by this strip
     int wmax = max(lastca, lastcb);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d, 64));
-    for (int i = t; i < 2 * SL * GSR_SLOT_FLOATS; i += 128) (&acc[0][0])[i] = 0.f;
+    for (int i = t; i < 2 * GSR_BWB * GSR_SLOT_FLOATS; i += 128) (&acc[0][0])[i] = 0.f;
     uint16_t* mylist = sList[wave];
-    const uint32_t qmask = 3u << (2 * wave);  // the two 8x8 quadrants of this strip
     int accfield = -1;  // accumulator field this lane reports after the wave reduction (see gsr_bank_reduce)
     {
         const int row = lane >> 4, bank = (lane >> 2) & 3;
@@ -1020,94 +944,62 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 
         }
     }
 
-    // back to front, in batches of GSR_SEG_LEN instances (one batch, except in a tile's last segment); local j = 0 is
-    // the backmost instance of the batch
-    // (SL = the batch length the LDS arrays are sized for; the segment, i.e. the checkpoint spacing seg_len, may be longer)
-    unsigned long long bandm64 = ~0ull;  // (the 128-entry form checks every instance)
+    // back to front, in batches of GSR_BWB instances (one batch per first-tier segment of a 64-position launch, more in the longer
+    // segments); local j = 0 is the backmost instance of the batch
     // a tile whose list was sorted a second time (it ran off its partially sorted prefix) lost the flags of its first pass: there
     // every instance is checked
     const bool band_flags_valid = need_full[tile] == 0u;
-    (void)bandm64; (void)band_flags_valid;  // (unused in the parity build)
-    for (int hi = seg_hi; hi > seg_lo; hi -= SL) {
-        const int lo = max(seg_lo, hi - SL), cnt = hi - lo;
-        if (SL == 64) {
-            // both wavefronts stage: wave 0 fetches {a, b} of instance `lane`, wave 1 {c, d} + the slot offset; the strip
-            // test below then runs on both (one box test per wave and instance instead of four quadrant tests on wave 0)
-            uint32_t idf = 0u;
-            if (lane < cnt) idf = point_list[rg.x + (hi - 1 - lane)];
+    (void)band_flags_valid;  // (unused in the parity build)
+    for (int hi = seg_hi; hi > seg_lo; hi -= GSR_BWB) {
+        const int lo = max(seg_lo, hi - GSR_BWB), cnt = hi - lo;
+        // both wavefronts stage: wave 0 fetches {a, b} of instance `lane`, wave 1 {c, d} + the slot offset; the strip
+        // test below then runs on both (one box test per wave and instance instead of four quadrant tests on wave 0)
+        uint32_t idf = 0u;
+        if (lane < cnt) idf = point_list[rg.x + (hi - 1 - lane)];
 #ifndef GSR_PRECISE_MATH
-            bandm64 = band_flags_valid ? __ballot((idf >> 31) != 0u) : ~0ull;  // batch slots the forward met inside the guard band (see gsr_blend_fwd_kernel)
+        const unsigned long long bandm64 = band_flags_valid ? __ballot((idf >> 31) != 0u) : ~0ull;  // batch slots the forward met inside the guard band (see gsr_blend_fwd_kernel)
 #endif
-            if (lane < cnt) {
-                const uint32_t id = idf & 0x7fffffffu;
-                const GsrRec* r = rec + id;
-                if (wave == 0) {
-#ifdef GSR_PRECISE_MATH
-                    sA[lane] = r->a; sB[lane] = r->b;
-#else
-                    const float4 a = r->a, b = r->b;  // raw conic -> the pre-scaled form the loop evaluates
-                    sA[lane] = make_float4(a.x, a.y, GSR_HA(a.z), GSR_HB(a.w)); sB[lane] = make_float4(GSR_HC(b.x), b.y, b.z, b.w);
-#endif
-                } else {
-                    const uint32_t slot0 = offsets[id];
-                    const uint4 d = r->d;
-                    const float4 c = r->c;
-                    const int x0 = d.y & 0xffff, y0 = d.y >> 16, wd = (int)d.x;
-                    const int pos = (ty - y0) * wd + (tx - x0);
-                    const unsigned long long mask = ((unsigned long long)d.w << 32) | d.z;
-                    sSlot[lane] = slot0 + (uint32_t)(pos < 64 ? __popcll(mask & ((1ull << pos) - 1ull)) : __popcll(mask) + (pos - 64));
-                    sC[lane] = c;
-                }
-            }
-        } else
-        if (t < cnt) {
-            const uint32_t id = point_list[rg.x + (hi - 1 - t)] & 0x7fffffffu;
+        if (lane < cnt) {
+            const uint32_t id = idf & 0x7fffffffu;
             const GsrRec* r = rec + id;
-            const uint32_t slot0 = offsets[id];  // first gradient slot of the Gaussian (exclusive scan of tiles[])
-            const uint4 d = r->d;
-            const float4 c = r->c;
-            // gradient slot = Gaussian's scan offset + rank of this tile among the surviving tiles of its rectangle
-            const int x0 = d.y & 0xffff, y0 = d.y >> 16, wd = (int)d.x;
-            const int pos = (ty - y0) * wd + (tx - x0);
-            const unsigned long long mask = ((unsigned long long)d.w << 32) | d.z;
-            sSlot[t] = slot0 + (uint32_t)(pos < 64 ? __popcll(mask & ((1ull << pos) - 1ull)) : __popcll(mask) + (pos - 64));
-            const float4 a = r->a, b = r->b;
-            sQ[t] = gsr_quadrant_mask(a, b, c.w * GSR_LOG2E, tx, ty, W, H);
+            if (wave == 0) {
 #ifdef GSR_PRECISE_MATH
-            sA[t] = a; sB[t] = b; sC[t] = c;
+                sA[lane] = r->a; sB[lane] = r->b;
 #else
-            sA[t] = make_float4(a.x, a.y, GSR_HA(a.z), GSR_HB(a.w)); sB[t] = make_float4(GSR_HC(b.x), b.y, b.z, b.w); sC[t] = c;
+                const float4 a = r->a, b = r->b;  // raw conic -> the pre-scaled form the loop evaluates
+                sA[lane] = make_float4(a.x, a.y, GSR_HA(a.z), GSR_HB(a.w)); sB[lane] = make_float4(GSR_HC(b.x), b.y, b.z, b.w);
 #endif
+            } else {
+                const uint32_t slot0 = offsets[id];
+                const uint4 d = r->d;
+                const float4 c = r->c;
+                const int x0 = d.y & 0xffff, y0 = d.y >> 16, wd = (int)d.x;
+                const int pos = (ty - y0) * wd + (tx - x0);
+                const unsigned long long mask = ((unsigned long long)d.w << 32) | d.z;
+                sSlot[lane] = slot0 + (uint32_t)(pos < 64 ? __popcll(mask & ((1ull << pos) - 1ull)) : __popcll(mask) + (pos - 64));
+                sC[lane] = c;
+            }
         }
         __syncthreads();
         {
             // instance j sits at list position p = hi-1-j; this wave needs it only if p < wmax
-            int nw;
-            if (SL == 64) {
-                bool hit = false;
-                if (lane < cnt && hi - 1 - lane < wmax) {
-                    const float4 a = sA[lane], b = sB[lane];
+            bool hit = false;
+            if (lane < cnt && hi - 1 - lane < wmax) {
+                const float4 a = sA[lane], b = sB[lane];
 #ifdef GSR_PRECISE_MATH
-                    const float ca = GSR_QSCALE(a.z), cb = GSR_QSCALE(a.w), cc = GSR_QSCALE(b.x);
+                const float ca = GSR_QSCALE(a.z), cb = GSR_QSCALE(a.w), cc = GSR_QSCALE(b.x);
 #else
-                    const float ca = -2.0f * a.z, cb = -a.w, cc = -2.0f * b.x;
+                const float ca = -2.0f * a.z, cb = -a.w, cc = -2.0f * b.x;
 #endif
-                    const int sx0 = tx * 16, sy0 = ty * 16 + wave * 8;  // this wavefront's 16x8 strip
-                    hit = sy0 < H && !(gsr_box_min_q(a.x, a.y, ca, cb, cc, GSR_RCP(ca), GSR_RCP(cc), (float)sx0, (float)min(sx0 + 15, W - 1),
-                                                     (float)sy0, (float)min(sy0 + 7, H - 1)) > sC[lane].w * GSR_LOG2E);  // (.w: the Gaussian's culling threshold)
-                }
-                const unsigned long long bal = __ballot(hit);
-                if (hit) mylist[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint16_t)lane;
-                nw = __popcll(bal);
-            } else {
-                nw = gsr_compact2<SL>(sQ, mylist, cnt, qmask, lane, [=](int i) { return hi - 1 - i < wmax; });
+                const int sx0 = tx * 16, sy0 = ty * 16 + wave * 8;  // this wavefront's 16x8 strip
+                hit = sy0 < H && !(gsr_box_min_q(a.x, a.y, ca, cb, cc, GSR_RCP(ca), GSR_RCP(cc), (float)sx0, (float)min(sx0 + 15, W - 1),
+                                                 (float)sy0, (float)min(sy0 + 7, H - 1)) > sC[lane].w * GSR_LOG2E);  // (.w: the Gaussian's culling threshold)
             }
+            const unsigned long long bal = __ballot(hit);
+            if (hit) mylist[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint16_t)lane;
+            const int nw = __popcll(bal);
             __builtin_amdgcn_wave_barrier();
-#ifdef GSR_BWD_NOLOOP  // diagnostic: everything but the instance loop (what a task costs around it)
-            for (int c0 = 0; c0 < 0; c0 += 64) {
-#else
             for (int c0 = 0; c0 < nw; c0 += 64) {
-#endif
                 const int m = min(64, nw - c0);
                 const int jj = mylist[min(c0 + lane, nw - 1)];
                 int j = __builtin_amdgcn_readlane(jj, 0);
@@ -1149,7 +1041,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SL == 
 #ifndef GSR_PRECISE_MATH
                         unsigned long long banda = 0ull, bandb = 0ull;
                         // (a second copy of the loop body without this test for batches with no flagged instance: no gain, 161 vs 158.5 us)
-                        if (SL != 64 || ((bandm64 >> (j & 63)) & 1ull)) {  // wave-uniform (j is scalar): the forward flagged this instance
+                        if ((bandm64 >> (j & 63)) & 1ull) {  // wave-uniform (j is scalar): the forward flagged this instance
                             banda = __builtin_amdgcn_ballot_w64(al.x < GSR_ALPHA_HI) & okma;
                             bandb = __builtin_amdgcn_ballot_w64(al.y < GSR_ALPHA_HI) & okmb;
                         }
@@ -1281,7 +1173,7 @@ hipError_t gsr_launch_blend_forward(int W, int H, int gx, int T, const float* bg
         qorder = image.qorder;
     }
 #define GSR_FWD_LAUNCH(TR)                                                                                                             \
-    hipLaunchKernelGGL(gsr_blend_fwd_kernel<TR>, dim3(32 * xt), dim3(64), GSR_FWD_LDS_PAD, stream, image.ranges, bin.point_list, geom.rec, W, H, \
+    hipLaunchKernelGGL(gsr_blend_fwd_kernel<TR>, dim3(32 * xt), dim3(64), 0, stream, image.ranges, bin.point_list, geom.rec, W, H, \
                        gx, T, bg, out_color, out_depth, out_feature, image.final_T, image.n_contrib, image.tile_work, image.ckpt,     \
                        gsr_seg_len(T), (uint32_t)capacity, max_tile_count < 0 ? 0x7fffffffu : (uint32_t)max_tile_count,               \
                        image.sorted_len, image.need_full, only_flagged ? image.need_full : (const uint32_t*)nullptr, image.qresume, image.info + 3,        \
@@ -1304,22 +1196,13 @@ hipError_t gsr_launch_blend_backward(int W, int H, int gx, int T, const float* b
     const int sl = gsr_seg_len(T);
     const int nseg = std::max(GSR_SEG1 + 1, gsr_segments_for(max_tile_count, sl));
     const dim3 grid(8u * (uint32_t)gsr_xcd_tiles(T) * (uint32_t)nseg);
-#define GSR_BWD_LAUNCH(A, SLEN, GD, GF)                                                                                          \
-    hipLaunchKernelGGL((gsr_blend_bwd_kernel<A, SLEN>), grid, dim3(128), 0, stream, image.ranges, bin.point_list, geom.rec, W, H, \
+#define GSR_BWD_LAUNCH(A, GD, GF)                                                                                                \
+    hipLaunchKernelGGL(gsr_blend_bwd_kernel<A>, grid, dim3(128), 0, stream, image.ranges, bin.point_list, geom.rec, W, H, \
                        gx, bg, image.final_T, image.n_contrib, image.ckpt, dL_dcolor, GD, GF, image.tile_work, T, sl,            \
                        geom.offsets, slot_written, s4, heavy_groups, image.need_full, nseg, image.info + 3, gsr_xcd_tiles(T))
-#ifdef GSR_BWD_BATCH128  // long segments staged 128 instances at a time (19.5 KB of LDS: 4 waves per SIMD)
-    const bool b64 = sl == 64;
-#else                    // long segments in two batches of 64 (9.7 KB: 5 waves per SIMD)
-    const bool b64 = true;
-#endif
-    if (dL_ddepth || dL_dfeature) {
-        if (b64) GSR_BWD_LAUNCH(true, 64, dL_ddepth, dL_dfeature);
-        else GSR_BWD_LAUNCH(true, GSR_SEG_LEN, dL_ddepth, dL_dfeature);
-    } else {
-        if (b64) GSR_BWD_LAUNCH(false, 64, nullptr, nullptr);
-        else GSR_BWD_LAUNCH(false, GSR_SEG_LEN, nullptr, nullptr);
-    }
+    // (segments of 128 positions are staged as two batches of GSR_BWB = 64: 9.7 KB of LDS per workgroup)
+    if (dL_ddepth || dL_dfeature) GSR_BWD_LAUNCH(true, dL_ddepth, dL_dfeature);
+    else GSR_BWD_LAUNCH(false, nullptr, nullptr);
 #undef GSR_BWD_LAUNCH
     return hipGetLastError();
 }

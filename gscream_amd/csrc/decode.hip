@@ -43,16 +43,10 @@ struct GsdMlps {  // device pointers; m = 0 opacity (K, tanh), 1 uncertainty (K,
 
 // sigmoid through the hardware exp2 / reciprocal (each within 1 ulp): relative error ~3e-7, far inside the 2e-5 the outputs
 // are held to; the IEEE expf + division of the first version cost ~25 VALU instructions per value, 21 values per lane
-// and 16-anchor step -- as much SIMD time as the matrix-core products themselves (-DGSD_PRECISE_ACT restores it).
-#ifdef GSD_PRECISE_ACT
-__device__ __forceinline__ float gsd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float gsd_rcp(float x) { return 1.0f / x; }
-__device__ __forceinline__ float gsd_tanh(float x) { return tanhf(x); }
-#else
+// and 16-anchor step -- as much SIMD time as the matrix-core products themselves.
 __device__ __forceinline__ float gsd_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 __device__ __forceinline__ float gsd_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float gsd_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x)); }  // backward only: enters as 1 - t^2
-#endif
 
 // ---- the MLPs on the f32 matrix cores ----------------------------------------------------------------------------------
 // v_mfma_f32_16x16x4_f32 computes D[16x16] += A[16x4] B[4x16]; lane l = (g = l >> 4, a = l & 15) supplies A[row a][k g] and

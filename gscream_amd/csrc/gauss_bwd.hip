@@ -283,10 +283,6 @@ __global__ void __launch_bounds__(64, GSR_K7_WAVES) gsr_gauss_bwd_kernel(const G
     constexpr int WCH = 128;  // written slots staged per sub-pass (48 B each)
     __shared__ float4 stage[WCH * 3];
     __shared__ uint16_t wl[FCH];
-#ifdef GSR_K7_BYTE_FLAGS
-    __shared__ unsigned long long gmask[FCH / 64];
-    __shared__ uint32_t gbase[FCH / 64 + 1];
-#endif
     const int P = A.P, num_slots = A.num_slots;
     const uint32_t* __restrict__ offsets = A.offsets;
     const float4* __restrict__ slots = A.slots;
@@ -335,7 +331,6 @@ __global__ void __launch_bounds__(64, GSR_K7_WAVES) gsr_gauss_bwd_kernel(const G
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, d, 64));
     const bool spread = cmax > 24u;
-#ifndef GSR_K7_BYTE_FLAGS
     for (uint32_t base = S0, nf; base < S1; base += nf) {
         // One 8-byte load per lane covers the 512 flag bytes from the 8-aligned address below `base` (every pass but the
         // first starts aligned); lane l holds the flags of slots base - shift + 8 l + k, k = 0..7, as bit k of m.
@@ -367,29 +362,6 @@ __global__ void __launch_bounds__(64, GSR_K7_WAVES) gsr_gauss_bwd_kernel(const G
             ci0 = lo < nf ? (p0 >> 8) + (uint32_t)__popc(p0 & 0xffu & ((1u << (a0 & 7u)) - 1u)) : run;
             ci1 = hi < nf ? (p1 >> 8) + (uint32_t)__popc(p1 & 0xffu & ((1u << (a1 & 7u)) - 1u)) : run;
         }
-#else
-    for (uint32_t base = S0, nf; base < S1; base += nf) {
-        nf = min(S1 - base, (uint32_t)FCH);
-        uint8_t f[FCH / 64];
-#pragma unroll
-        for (int k = 0; k < FCH / 64; k++) {
-            const uint32_t i = k * 64 + lane;
-            f[k] = i < nf ? slot_written[base + i] : (uint8_t)0;
-        }
-        uint32_t run = 0;
-#pragma unroll
-        for (int k = 0; k < FCH / 64; k++) {
-            const unsigned long long mk = __ballot(f[k] != 0);
-            if (f[k]) wl[run + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = (uint16_t)(k * 64 + lane);
-            if (lane == 0) { gmask[k] = mk; gbase[k] = run; }
-            run += (uint32_t)__popcll(mk);
-        }
-        __syncthreads();
-        const uint32_t lo = min(max(off, base), base + nf) - base, hi = min(max(off + cnt, base), base + nf) - base;
-        uint32_t ci0 = run, ci1 = run;
-        if (lo < nf) ci0 = gbase[lo >> 6] + (uint32_t)__popcll(gmask[lo >> 6] & ((1ull << (lo & 63)) - 1ull));
-        if (hi < nf) ci1 = gbase[hi >> 6] + (uint32_t)__popcll(gmask[hi >> 6] & ((1ull << (hi & 63)) - 1ull));
-#endif
         any_written |= run;
         for (uint32_t w0 = 0; w0 < run; w0 += WCH) {
             const uint32_t nw = min(run - w0, (uint32_t)WCH);

@@ -39,12 +39,10 @@
 #include "../../include/gsraster.h"
 
 #define GSR_TILE 16
-#ifndef GSR_MAX_CHUNKS
+// (plain #defines where gscream_amd/_layout.py mirrors the value: a -D of one of them collides instead of building a library the mirror mis-decodes)
 #define GSR_MAX_CHUNKS 256       // NB: rows of the (chunk, tile) count table = workgroups of the histogram / scatter launches: one per CU
-#endif                           // (measured at 1M Gaussians: 2048 x 128 threads 47 + 47 us, 1024 x 256: 36 + 44, 512 x 512: 32 + 41, 256 x 1024: 29 + 38)
-#ifndef GSR_CHUNK_GAUSS
+                                 // (measured at 1M Gaussians: 2048 x 128 threads 47 + 47 us, 1024 x 256: 36 + 44, 512 x 512: 32 + 41, 256 x 1024: 29 + 38)
 #define GSR_CHUNK_GAUSS 1024     // Gaussians per chunk at least (small clouds get fewer chunks, large ones GSR_MAX_CHUNKS bigger chunks)
-#endif
 #ifndef GSR_HIST_THREADS
 #define GSR_HIST_THREADS 1024
 #endif
@@ -62,9 +60,7 @@
 // 164, config 3 -1 %, config 2 +-0, config 4 +0.3 % (its uniform slab had nothing to balance and loses some L2 sharing between
 // rows); chunks of 1 / 16 / one row and 4x4-tile blocks on a skewed XCD pattern measured the same or worse.  Index arithmetic with
 // compile-time divisors only: every workgroup of the grid runs it, the empty ones too.
-#ifndef GSR_XCD_CHUNK
 #define GSR_XCD_CHUNK 4
-#endif
 static __host__ __device__ __forceinline__ int gsr_xcd_tiles(int T)  // tile slots per XCD (the last chunks may be partly or wholly beyond T)
 {
     return (((T + GSR_XCD_CHUNK - 1) / GSR_XCD_CHUNK + 7) / 8) * GSR_XCD_CHUNK;
@@ -122,7 +118,6 @@ __device__ __forceinline__ void gsr_fwd_order_block(int x, int T, int xt, const 
 #endif
 }
 #define GSR_SLOT_FLOATS 12
-#define GSR_SEG_LEN 128          // longest depth segment of a tile list = instances per backward task (LDS provision)
 // Depth segments of a tile's list (= backward tasks; the forward leaves a checkpoint at every boundary), in THREE TIERS at FIXED list
 // positions (rounds 5, 6):
 //   tier 1: GSR_SEG1 = 7 segments of the launch's segment length L (64 / 128) -- the fine cut the bench-like frames live in (their
@@ -143,23 +138,14 @@ __device__ __forceinline__ void gsr_fwd_order_block(int x, int T, int xt, const 
 // i.e. changed how the forward's segment sums associate: images and gradients differed in the last bit with the knob
 // (tools/fuzz_parity.py, case 5049).
 #define GSR_SEG1 7
-#ifndef GSR_T2_LEN
 #define GSR_T2_LEN 3     // length of a second-tier segment in units of L
-#endif
-#ifndef GSR_T2_N
 #define GSR_T2_N 6       // second-tier segments
-#endif
-#ifndef GSR_SEG3_LEN
 #define GSR_SEG3_LEN 8   // length of a third-tier segment in units of L
-#endif
-#ifndef GSR_SEG2
 #define GSR_SEG2 20      // segments behind the first tier: GSR_T2_N of the second tier + 13 of the third + the rest
-#endif
 #define GSR_SEG_MAX (GSR_SEG1 + GSR_SEG2)   // segments per tile = checkpoint slots (GSR_SEG_MAX - 1 checkpoints + the "last" slot)
 #define GSR_CKPT_PLANES (GSR_SEG_MAX * 6)
-// (kept for the call sites: the unit of the boundaries behind tier 1 is the launch's segment length, whatever the list length)
-__host__ __device__ static inline int gsr_seg2_len(int /* n */, int L) { return L; }
-// list position of checkpoint k (k = 0 .. GSR_SEG_MAX-2) = end of segment k = start of segment k + 1
+// list position of checkpoint k (k = 0 .. GSR_SEG_MAX-2) = end of segment k = start of segment k + 1.  `unit`, the unit of the boundaries
+// behind tier 1, is the launch's segment length L at every call site, whatever the list length
 __host__ __device__ static inline int gsr_ckpt_pos(int k, int L, int unit)
 {
     static_assert(GSR_SEG2 > GSR_T2_N + 1, "tiers");

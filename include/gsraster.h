@@ -202,8 +202,10 @@ int gsr_forward(int P, int D, int M, int W, int H,
 int gsr_backward(int P, int D, int M, int W, int H, int R, int binning_capacity /* what the forward's binning
                  workspace was sized for; = R after the two-stage forward */,
                  int max_tile_count /* gsr_stage1_result.max_tile_count of THAT forward (its longest per-tile list), or <= 0 if the
-                 caller did not keep it: sizes the grid of depth-segment tasks -- a frame none of whose lists reaches the second
-                 segment tier needs half the workgroups; unknown = the full grid, same results */,
+                 caller did not keep it: the grid of depth-segment tasks covers the segments of lists up to that length (workgroups
+                 of segments no list reaches would only be dispatched to leave at once); unknown = the full grid, same results.  A
+                 SMALLER figure than the true one is safe: the grid's last segment takes the rest of every list, so longer lists are
+                 still traversed completely, by one longer task -- the figure is a performance hint, not a bound */,
                  const float* background,
                  const float* means3D, const int32_t* radii, const float* colors_precomp, const float* shs,
                  const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,

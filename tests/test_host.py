@@ -225,7 +225,7 @@ def test_init_state_generator_follows_create_from_pcd():
 
 
 def test_segment_position_helpers_mirror_the_header():
-    """gscream_amd/_layout.py seg2_len / ckpt_pos = gsr_common.h gsr_seg2_len / gsr_ckpt_pos: seven segments of L, six of 3 L, then
+    """gscream_amd/_layout.py seg2_len / ckpt_pos = gsr_common.h gsr_ckpt_pos and its unit: seven segments of L, six of 3 L, then
     segments of 8 L (round 6), all at FIXED list positions (they must not follow the list length: the occlusion cut-off shortens lists
     behind everything that blends, and moving boundaries would re-associate the forward's sums), then the rest.  (The GPU kernels and
     this mirror are compared through the checkpoints in test_second_tier_of_depth_segments.)"""
