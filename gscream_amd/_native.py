@@ -21,6 +21,7 @@ EXPORTED_SYMBOLS = (
     "gsr_depth_loss_workspace_bytes", "gsr_depth_loss_forward", "gsr_depth_loss_backward", "gsr_training_stats",
     "gsr_decode_weight_grad_workspace_bytes", "gsr_decode_zero_hidden_rows", "gsr_decode_visible_rows", "gsr_adaptive_reset",
     "gsr_anchor_grow_workspace_bytes", "gsr_anchor_grow_keys", "gsr_anchor_grow_emit", "gsr_scatter_max",
+    "gsr_crossattn_workspace_bytes", "gsr_crossattn_forward", "gsr_crossattn_backward",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -147,6 +148,12 @@ def load():
     lib.gsr_anchor_grow_emit.argtypes = [_c_int] * 5 + [_vp] * 4 + [_c_float] + [_vp] * 5
     lib.gsr_scatter_max.restype = _c_int
     lib.gsr_scatter_max.argtypes = [_c_int] * 3 + [_vp] * 5
+    lib.gsr_crossattn_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_crossattn_workspace_bytes.argtypes = [_c_int] * 4
+    lib.gsr_crossattn_forward.restype = _c_int
+    lib.gsr_crossattn_forward.argtypes = [_c_int] * 5 + [_vp] * 6 + [_c_float] + [_vp] * 4
+    lib.gsr_crossattn_backward.restype = _c_int
+    lib.gsr_crossattn_backward.argtypes = [_c_int] * 5 + [_vp] * 6 + [_c_float] + [_vp] * 10
     _lib = lib
     return lib
 

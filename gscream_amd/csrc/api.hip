@@ -919,3 +919,46 @@ extern "C" int gsr_scatter_max(int R, int F, int S, const float* src, const int6
     GSR_HIP(gag_launch_scatter_max(R, F, S, src, index, out, argmax, (hipStream_t)stream), "scatter_max");
     return GSR_OK;
 }
+
+// ---- bidirectional cross-attention core (crossattn.hip) ----
+static int gca_check_sizes(const char* what, int B, int H, int I, int J, int dim_head)
+{
+    if (dim_head != 64) return gsr_fail(GSR_ERR_UNSUPPORTED, "%s: dim_head = %d (this path is built for 64)", what, dim_head);
+    if (B < 1 || H < 1 || I < 1 || J < 1 || (long long)B * H > 65535 || (long long)B * H * ((long long)I + J) * 64 > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes b=%d heads=%d i=%d j=%d", what, B, H, I, J);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_crossattn_workspace_bytes(int B, int H, int I, int J)
+{
+    if (B < 1 || H < 1 || I < 1 || J < 1) return 0;
+    return gca_workspace_bytes(B, H, I, J);
+}
+
+extern "C" int gsr_crossattn_forward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                                     const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale, float* out,
+                                     float* context_out, void* workspace, void* stream)
+{
+    if (int rc = gca_check_sizes("crossattn forward", B, H, I, J, dim_head)) return rc;
+    if (!qk || !v || !context_qk || !context_v || !out || !context_out || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "crossattn forward: a required pointer is NULL");
+    GSR_HIP(gca_launch_forward(B, H, I, J, qk, v, context_qk, context_v, mask, context_mask, scale, out, context_out, workspace,
+                               (hipStream_t)stream),
+            "crossattn forward");
+    return GSR_OK;
+}
+
+extern "C" int gsr_crossattn_backward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                                      const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale,
+                                      const float* out, const float* context_out, const float* d_out, const float* d_context_out,
+                                      void* workspace, float* d_qk, float* d_v, float* d_context_qk, float* d_context_v, void* stream)
+{
+    if (int rc = gca_check_sizes("crossattn backward", B, H, I, J, dim_head)) return rc;
+    if (!qk || !v || !context_qk || !context_v || !out || !context_out || !d_out || !d_context_out || !workspace || !d_qk || !d_v
+        || !d_context_qk || !d_context_v)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "crossattn backward: a required pointer is NULL");
+    GSR_HIP(gca_launch_backward(B, H, I, J, qk, v, context_qk, context_v, mask, context_mask, scale, out, context_out, d_out,
+                                d_context_out, workspace, d_qk, d_v, d_context_qk, d_context_v, (hipStream_t)stream),
+            "crossattn backward");
+    return GSR_OK;
+}

@@ -412,3 +412,13 @@ hipError_t gag_launch_emit(int N, int K, int F, int L, int M, const float* feat,
                            const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor, float* new_feat, int32_t* info,
                            hipStream_t stream);
 hipError_t gag_launch_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, hipStream_t stream);
+
+// ---- crossattn.hip (the attention core of BidirectionalCrossAttention: both softmax directions, forward and backward) ----
+size_t gca_workspace_bytes(int B, int H, int I, int J);
+hipError_t gca_launch_forward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
+                              const uint8_t* mask, const uint8_t* cmask, float scale, float* out, float* cout, void* workspace,
+                              hipStream_t stream);
+hipError_t gca_launch_backward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
+                               const uint8_t* mask, const uint8_t* cmask, float scale, const float* out, const float* cout,
+                               const float* d_out, const float* d_cout, void* workspace, float* d_qk, float* d_v, float* d_cqk,
+                               float* d_cv, hipStream_t stream);

@@ -327,6 +327,29 @@ int gsr_anchor_grow_emit(int N, int K, int F, int L, int M, const float* anchor_
 int gsr_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, void* stream);
 
 /*
+ * The attention core of BidirectionalCrossAttention (bidirectional-cross-attention 0.0.4, GaussianModel.run_crossattn,
+ * scene/gaussian_model.py:553-583): everything between the input projections and the output projections, for both directions.
+ *     sim[b,h,i,j]   = scale * qk[b,i,h,:] . context_qk[b,j,h,:];  a pair with mask[b,i] & context_mask[b,j] false takes -FLT_MAX
+ *     out[b,i,h,:]         = sum_j softmax_j(sim) context_v[b,j,h,:]
+ *     context_out[b,j,h,:] = sum_i softmax_i(sim) v[b,i,h,:]
+ * qk, v, out: [B,I,H,64]; context_qk, context_v, context_out: [B,J,H,64] -- the layout nn.Linear leaves ([b, n, h*d] contiguous),
+ * fp32.  mask [B,I], context_mask [B,J]: one byte per entry (torch.bool), NULL = all true.  dim_head must be 64
+ * (GSR_ERR_UNSUPPORTED otherwise).  fp32 on the exact f32 matrix cores; no [h,i,j] tensor is written.  The forward leaves each
+ * softmax row's (max, 1 / sum) in the workspace (gsr_crossattn_workspace_bytes(B, H, I, J)); the backward takes the same inputs,
+ * both outputs (not read at present: the kernels recompute what they need from the inputs and the workspace), the two output
+ * gradients and that workspace (it also uses it as scratch) and writes the four input gradients.
+ * No atomics: repeated calls give identical bits.
+ */
+size_t gsr_crossattn_workspace_bytes(int B, int H, int I, int J);
+int gsr_crossattn_forward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                          const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale, float* out,
+                          float* context_out, void* workspace, void* stream);
+int gsr_crossattn_backward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                           const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale, const float* out,
+                           const float* context_out, const float* d_out, const float* d_context_out, void* workspace, float* d_qk,
+                           float* d_v, float* d_context_qk, float* d_context_v, void* stream);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
