@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = (
     "gsr_decode_weight_grad_workspace_bytes", "gsr_decode_zero_hidden_rows", "gsr_decode_visible_rows", "gsr_adaptive_reset",
     "gsr_anchor_grow_workspace_bytes", "gsr_anchor_grow_keys", "gsr_anchor_grow_emit", "gsr_scatter_max",
     "gsr_crossattn_workspace_bytes", "gsr_crossattn_forward", "gsr_crossattn_backward",
+    "gsr_anchor_sample_workspace_bytes", "gsr_anchor_sample",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -154,6 +155,10 @@ def load():
     lib.gsr_crossattn_forward.argtypes = [_c_int] * 5 + [_vp] * 6 + [_c_float] + [_vp] * 4
     lib.gsr_crossattn_backward.restype = _c_int
     lib.gsr_crossattn_backward.argtypes = [_c_int] * 5 + [_vp] * 6 + [_c_float] + [_vp] * 10
+    lib.gsr_anchor_sample_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_anchor_sample_workspace_bytes.argtypes = [_c_int, _c_int]
+    lib.gsr_anchor_sample.restype = _c_int
+    lib.gsr_anchor_sample.argtypes = [_c_int] * 3 + [_vp] * 4 + [_c_int] * 5 + [ctypes.c_uint64] + [_vp] * 7
     _lib = lib
     return lib
 

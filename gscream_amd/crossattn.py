@@ -18,7 +18,8 @@ Every other form runs the torch expressions above: a different form, not a missi
 `module.last_path` says which one the last call took ("hip" / "torch").
 
 `run_crossattn`, `crossattn_param_group` and `crossattn_lr` are GaussianModel.run_crossattn (:553-583), the optimizer_c group (:396-409)
-and its learning-rate schedule (:450-453)."""
+and its learning-rate schedule (:450-453).  `run_crossattn_rows` is run_crossattn on ascending row lists instead of boolean masks
+(what gscream_amd/anchor_sampler.py produces): the same bits, no nonzero and so no host stop."""
 import ctypes
 import math
 
@@ -27,7 +28,7 @@ from torch import nn
 
 from . import _native
 
-__all__ = ["BidirectionalCrossAttention", "run_crossattn", "crossattn_param_group", "crossattn_optimizer", "crossattn_lr"]
+__all__ = ["BidirectionalCrossAttention", "run_crossattn", "run_crossattn_rows", "crossattn_param_group", "crossattn_optimizer", "crossattn_lr"]
 
 HIP_DIM_HEAD = 64
 
@@ -171,6 +172,33 @@ def run_crossattn(model, fg_anchor_mask, bg_anchor_mask, pe=False, ema=1.0, is_r
         model._anchor_feat[fg_anchor_mask] = ema * fg_feat_out[0, :, :] + (1 - ema) * model._anchor_feat[fg_anchor_mask]
     # always update the bg feature
     model._anchor_feat[bg_anchor_mask] = ema * bg_feat_out[0, :, :] + (1 - ema) * model._anchor_feat[bg_anchor_mask]
+
+    model._anchor_feat.retain_grad()
+    return
+
+
+def run_crossattn_rows(model, fg_rows, bg_rows, pe=False, ema=1.0, is_ref=True):
+    """run_crossattn with the two anchor sets given as ASCENDING int64 row tensors (the nonzeros of its masks, in `feat[mask]` order):
+    index_select / index_copy_ in the place of the boolean-mask gathers and assignments, each of which is a nonzero plus a size
+    read-back.  Bit-identical to the mask form for the same sets, values and gradients."""
+    assert fg_rows.dim() == 1 and bg_rows.dim() == 1 and fg_rows.dtype == bg_rows.dtype == torch.int64
+    if pe:
+        raise NotImplementedError("run_crossattn_rows(pe=True): the positional-embedding branch is commented out in the reference (:561-563)")
+
+    _rebind_anchor_feat(model, model._anchor_feat.detach())
+
+    fg_feat = model._anchor_feat.index_select(0, fg_rows)[None, :, :].clone()  # 1, N, 32
+    bg_feat = model._anchor_feat.index_select(0, bg_rows)[None, :, :].clone()  # 1, N, 32
+
+    fg_feat_mask = torch.ones_like(fg_feat[:, :, 0]).bool()
+    bg_feat_mask = torch.ones_like(bg_feat[:, :, 0]).bool()
+
+    fg_feat_out, bg_feat_out = model.crossattn(fg_feat, bg_feat, mask=fg_feat_mask, context_mask=bg_feat_mask)
+
+    if is_ref:  # only update the fg feature under reference view
+        model._anchor_feat.index_copy_(0, fg_rows, ema * fg_feat_out[0, :, :] + (1 - ema) * model._anchor_feat.index_select(0, fg_rows))
+    # always update the bg feature
+    model._anchor_feat.index_copy_(0, bg_rows, ema * bg_feat_out[0, :, :] + (1 - ema) * model._anchor_feat.index_select(0, bg_rows))
 
     model._anchor_feat.retain_grad()
     return

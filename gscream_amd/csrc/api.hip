@@ -962,3 +962,31 @@ extern "C" int gsr_crossattn_backward(int B, int H, int I, int J, int dim_head, 
             "crossattn backward");
     return GSR_OK;
 }
+
+// ---- cross-attention anchor sampler (anchor_sample.hip) ----
+static int gas_check_sizes(int N, int H, int W, int max_pairs)
+{
+    if (N < 0 || N > 0x7fffff00 || max_pairs < 0 || H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || (long long)H * W > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor sample: bad sizes N=%d H=%d W=%d max_pairs=%d", N, H, W, max_pairs);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_anchor_sample_workspace_bytes(int N, int max_pairs)
+{
+    if (N < 0 || N > 0x7fffff00 || max_pairs < 0) return 0;
+    return gas_workspace_bytes(N, max_pairs);
+}
+
+extern "C" int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask,
+                                 int min_y, int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace,
+                                 uint8_t* src_mask, uint8_t* dst_mask, int64_t* src_rows, int64_t* dst_rows, int32_t* info, void* stream)
+{
+    if (int rc = gas_check_sizes(N, H, W, max_pairs)) return rc;
+    if (!info || (N > 0 && (!workspace || !visible || !px || !py || !gt_mask || !src_mask || !dst_mask))
+        || (N > 0 && max_pairs > 0 && (!src_rows || !dst_rows)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor sample: a required pointer is NULL");
+    GSR_HIP(gas_launch(N, H, W, visible, px, py, gt_mask, min_y, max_y, min_x, max_x, max_pairs, seed, workspace, src_mask, dst_mask,
+                       src_rows, dst_rows, info, (hipStream_t)stream),
+            "anchor sample");
+    return GSR_OK;
+}

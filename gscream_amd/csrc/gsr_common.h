@@ -422,3 +422,9 @@ hipError_t gca_launch_backward(int B, int H, int I, int J, const float* qk, cons
                                const uint8_t* mask, const uint8_t* cmask, float scale, const float* out, const float* cout,
                                const float* d_out, const float* d_cout, void* workspace, float* d_qk, float* d_v, float* d_cqk,
                                float* d_cv, hipStream_t stream);
+
+// ---- anchor_sample.hip (the cross-attention anchor sampler of train.py:436-511: classify, count, keyed radix select, ordered compaction) ----
+size_t gas_workspace_bytes(int N, int max_pairs);
+hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask, int min_y,
+                      int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace, uint8_t* src_mask, uint8_t* dst_mask,
+                      int64_t* src_rows, int64_t* dst_rows, int32_t* info, hipStream_t stream);

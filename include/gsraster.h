@@ -350,6 +350,31 @@ int gsr_crossattn_backward(int B, int H, int I, int J, int dim_head, const float
                            float* d_v, float* d_context_qk, float* d_context_v, void* stream);
 
 /*
+ * The anchor sampler of the cross-attention step (train.py:436-511), without a host stop: from what prefilter_position2D
+ * returns (visible[N] one byte per anchor, px[N], py[N] fp32), the view's mask gt_mask[H,W] (fp32) and the patch rectangle, the
+ * two anchor sets GaussianModel.run_crossattn pairs up.  Per anchor a, x = px[a], y = py[a]:
+ *     valid    visible[a] and 0 < x < W and 0 < y < H  (strict, floating point; NaN is invalid);  pixel (iy, ix) = ((int)y, (int)x)
+ *     sampled  valid and min_y <= iy < max_y and min_x <= ix < max_x  (an empty or inverted rectangle samples nothing)
+ *     label    (long)gt_mask[iy, ix];  fg: sampled and label > 0;  bg: sampled and label == 0;  a negative label is in neither
+ *     ok       n_fg > 11 and n_bg > 11;   min_num = min(n_fg, n_bg, max_pairs)
+ *     src / dst  the min_num members of fg / bg with the smallest (key, index): a uniformly random min_num-subset of the class
+ * key, modulo 2^32, with s_lo / s_hi the halves of `seed` and i the anchor index:
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     key(i) = mix(((mix((i ^ s_lo) + s_hi)) + s_lo) ^ s_hi)        (a bijection of uint32: keys never tie)
+ * Writes src_mask[N], dst_mask[N] (one byte per anchor, 0 / 1, every entry), the selected anchor indices in ASCENDING order in
+ * src_rows[0:min_num], dst_rows[0:min_num] (the order of feat[mask]; entries from min_num on are left untouched) and
+ * info[8] = {n_sampled, n_fg, n_bg, min_num, ok, 0, 0, 0} (int32, on the device).  When ok == 0 the masks are all zero and min_num
+ * is still reported.  N == 0 is valid.  Integer atomics only: repeated calls give identical bits.  A fixed number of launches on
+ * `stream`, no read-back.  workspace: gsr_anchor_sample_workspace_bytes(N, max_pairs).
+ */
+size_t gsr_anchor_sample_workspace_bytes(int N, int max_pairs);
+int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask /* [H,W] */,
+                      int min_y, int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace,
+                      uint8_t* src_mask /* [N] */, uint8_t* dst_mask /* [N] */,
+                      int64_t* src_rows /* [max_pairs] */, int64_t* dst_rows /* [max_pairs] */,
+                      int32_t* info /* [8]: n_sampled, n_fg, n_bg, min_num, ok, 0, 0, 0 */, void* stream);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
