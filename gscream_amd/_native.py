@@ -7,6 +7,8 @@ through the CPU oracle or through eager PyTorch.
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSR_LIB") or os.path.join(_HERE, "libgsraster.so")  # GSR_LIB: diagnostic builds
 
@@ -64,7 +66,7 @@ def load():
         abi = int(lib.gsr_abi_version())
     except AttributeError:
         abi = None
-    if abi != ABI_VERSION and not os.environ.get("GSR_SKIP_ABI_CHECK"):  # (the knob: A/B runs against an older build, tools/)
+    if abi != ABI_VERSION and not os.environ.get("GSR_SKIP_ABI_CHECK"):  # (the knob: tools/cut_probe.py, tools/gpu_ab.sh)
         raise RuntimeError(f"gscream_amd: {LIB_PATH} has C-ABI version {abi}, this binding needs {ABI_VERSION} "
                            "(rebuild with `make -C gscream_amd/csrc`)")
     lib.gsr_version.restype = ctypes.c_char_p
@@ -97,14 +99,12 @@ def load():
     lib.gsr_mark_visible.argtypes = [_c_int] + [_vp] * 5
     lib.gsr_profile_begin.restype = _c_int
     lib.gsr_profile_begin.argtypes = [ctypes.c_uint]
-    if hasattr(lib, "gsr_profile_begin_sampled") or not os.environ.get("GSR_SKIP_ABI_CHECK"):  # (absent from an older build in an A/B run)
-        lib.gsr_profile_begin_sampled.restype = _c_int
-        lib.gsr_profile_begin_sampled.argtypes = [ctypes.c_uint, ctypes.c_uint]
+    lib.gsr_profile_begin_sampled.restype = _c_int
+    lib.gsr_profile_begin_sampled.argtypes = [ctypes.c_uint, ctypes.c_uint]
     lib.gsr_profile_end.restype = _c_int
     lib.gsr_profile_end.argtypes = [ctypes.POINTER(Profile)]
-    if hasattr(lib, "gsr_adaptive_reset") or not os.environ.get("GSR_SKIP_ABI_CHECK"):
-        lib.gsr_adaptive_reset.restype = None
-        lib.gsr_adaptive_reset.argtypes = []
+    lib.gsr_adaptive_reset.restype = None
+    lib.gsr_adaptive_reset.argtypes = []
     lib.gsr_stage_name.restype = ctypes.c_char_p
     lib.gsr_stage_name.argtypes = [_c_int]
     lib.gsr_loss_workspace_bytes.restype = ctypes.c_size_t
@@ -171,11 +171,7 @@ def profile_begin(stages=None, every=1):
     """Start timing stages with HIP events (all stages, or only the named ones to keep the stream undisturbed; every = n
     times only every n-th invocation of a stage)."""
     mask = 0 if not stages else sum(1 << STAGE_NAMES.index(s) for s in stages)
-    lib = load()
-    if os.environ.get("GSR_SKIP_ABI_CHECK") and not hasattr(lib, "gsr_profile_begin_sampled"):  # an older library in an A/B run (tools/gpu_ab_r3.sh)
-        check(lib.gsr_profile_begin(mask), "gsr_profile_begin")
-        return
-    check(lib.gsr_profile_begin_sampled(mask, int(every)), "gsr_profile_begin_sampled")
+    check(load().gsr_profile_begin_sampled(mask, int(every)), "gsr_profile_begin_sampled")
 
 
 def profile_end():
@@ -197,3 +193,40 @@ def ptr(t):
     if t is None or t.numel() == 0:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # the handle without building a torch.cuda.Stream
+
+
+def stream_handle(index):
+    """HIP stream handle of torch's current stream on device `index` (what the kernels are enqueued on)."""
+    if _raw_stream is not None:
+        return _raw_stream(index)
+    return torch.cuda.current_stream(index).cuda_stream
+
+
+class on_device:
+    """`with torch.cuda.device(dev)` that costs nothing when `dev` already is the current device (the training case)."""
+    __slots__ = ("index", "prev")
+
+    def __init__(self, index):
+        self.index, self.prev = index, -1
+
+    def __enter__(self):
+        cur = torch.cuda.current_device()
+        if cur != self.index:
+            self.prev = cur
+            torch.cuda.set_device(self.index)
+        return self.index
+
+    def __exit__(self, *exc):
+        if self.prev >= 0:
+            torch.cuda.set_device(self.prev)
+        return False
+
+
+def run(name, device, *args):
+    """lib.<name>(*args, stream) with `device` (a tensor's) current and on its current stream; raises unless it returns 0.
+    The caller keeps every tensor behind `args` referenced until this returns (the launches are then enqueued)."""
+    with on_device(device.index) as index:
+        check(getattr(load(), name)(*args, ctypes.c_void_p(stream_handle(index))), name)

@@ -12,7 +12,6 @@ anchors' cells, scatter_max of the features) is `grow_level`: HIP kernels around
 (gscream_amd/csrc/anchor_grow.hip), bit-identical to the reference expressions in the same row order.  A level whose
 candidate cells do not fit the keys (a cell outside [-2^20, 2^20) per axis, or a non-finite coordinate) runs the reference
 expressions in torch on the device instead (`reference_level`)."""
-import ctypes
 from functools import reduce
 
 import numpy as np
@@ -82,10 +81,8 @@ def grow_level(anchor, offset, scaling, anchor_feat, candidate_mask, cur_size):
     rows = torch.empty(L, dtype=torch.int32, device=dev)
     info = torch.empty(4, dtype=torch.int32, device=dev)
     P = _native.ptr
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.check(lib.gsr_anchor_grow_keys(N, K, L, P(anchor), P(offset), P(scaling), P(mask), inv, P(ws), P(keys), P(rows),
-                                               P(info), stream), "gsr_anchor_grow_keys")
+    with _native.on_device(dev.index):
+        _native.run("gsr_anchor_grow_keys", dev, N, K, L, P(anchor), P(offset), P(scaling), P(mask), inv, P(ws), P(keys), P(rows), P(info))
         M, flags = info[:2].tolist()
         if flags:
             return reference_level(anchor, offset, scaling, feat, candidate_mask, cur_size)
@@ -94,8 +91,7 @@ def grow_level(anchor, offset, scaling, anchor_feat, candidate_mask, cur_size):
         if M == 0:
             return cand, new_feat
         skeys, order = torch.sort(keys[:M], stable=True)  # torch.unique(dim=0)'s order; O(M log M) plumbing
-        _native.check(lib.gsr_anchor_grow_emit(N, K, F, L, M, P(feat), P(skeys), P(order), P(rows), size_f, P(ws), P(cand), P(new_feat),
-                                               P(info), stream), "gsr_anchor_grow_emit")
+        _native.run("gsr_anchor_grow_emit", dev, N, K, F, L, M, P(feat), P(skeys), P(order), P(rows), size_f, P(ws), P(cand), P(new_feat), P(info))
         C = int(info[2])
     return cand[:C], new_feat[:C]
 

@@ -105,12 +105,11 @@ def _sample_hip(visible, x, y, gt, rect, max_pairs, seed, src_rows, dst_rows):
     info = torch.empty(8, dtype=torch.int32, device=dev)
     ws = torch.empty(int(lib.gsr_anchor_sample_workspace_bytes(N, int(max_pairs))), dtype=torch.uint8, device=dev)
     min_y, max_y, min_x, max_x = (max(-(1 << 31), min((1 << 31) - 1, int(v))) for v in rect)
-    with torch.cuda.device(dev):
-        _native.check(lib.gsr_anchor_sample(
-            N, int(gt.shape[0]), int(gt.shape[1]), _native.ptr(visible), _native.ptr(x), _native.ptr(y), _native.ptr(gt), min_y, max_y,
-            min_x, max_x, int(max_pairs), ctypes.c_uint64(seed), _native.ptr(ws), _native.ptr(src_mask), _native.ptr(dst_mask),
-            _native.ptr(src_rows), _native.ptr(dst_rows), _native.ptr(info),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_anchor_sample")
+    _native.run(
+        "gsr_anchor_sample", dev,
+        N, int(gt.shape[0]), int(gt.shape[1]), _native.ptr(visible), _native.ptr(x), _native.ptr(y), _native.ptr(gt), min_y, max_y,
+        min_x, max_x, int(max_pairs), ctypes.c_uint64(seed), _native.ptr(ws), _native.ptr(src_mask), _native.ptr(dst_mask),
+        _native.ptr(src_rows), _native.ptr(dst_rows), _native.ptr(info))
     return src_mask, dst_mask, src_rows, dst_rows, info
 
 

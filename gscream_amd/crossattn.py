@@ -20,7 +20,6 @@ Every other form runs the torch expressions above: a different form, not a missi
 `run_crossattn`, `crossattn_param_group` and `crossattn_lr` are GaussianModel.run_crossattn (:553-583), the optimizer_c group (:396-409)
 and its learning-rate schedule (:450-453).  `run_crossattn_rows` is run_crossattn on ascending row lists instead of boolean masks
 (what gscream_amd/anchor_sampler.py produces): the same bits, no nonzero and so no host stop."""
-import ctypes
 import math
 
 import torch
@@ -47,11 +46,10 @@ class _AttentionCore(torch.autograd.Function):
             cmask = cmask.detach().to(torch.bool).contiguous()
         out, cout = torch.empty_like(qk), torch.empty_like(cqk)
         ws = torch.empty(int(lib.gsr_crossattn_workspace_bytes(B, heads, I, J)), dtype=torch.uint8, device=qk.device)
-        with torch.cuda.device(qk.device):
-            _native.check(lib.gsr_crossattn_forward(
-                B, heads, I, J, HIP_DIM_HEAD, _native.ptr(qk), _native.ptr(v), _native.ptr(cqk), _native.ptr(cv), _native.ptr(mask),
-                _native.ptr(cmask), scale, _native.ptr(out), _native.ptr(cout), _native.ptr(ws),
-                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_crossattn_forward")
+        _native.run(
+            "gsr_crossattn_forward", qk.device,
+            B, heads, I, J, HIP_DIM_HEAD, _native.ptr(qk), _native.ptr(v), _native.ptr(cqk), _native.ptr(cv), _native.ptr(mask),
+            _native.ptr(cmask), scale, _native.ptr(out), _native.ptr(cout), _native.ptr(ws))
         ctx.save_for_backward(qk, v, cqk, cv, out, cout, ws)
         ctx.masks, ctx.scale, ctx.heads = (mask, cmask), scale, heads
         return out, cout
@@ -59,18 +57,16 @@ class _AttentionCore(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out, d_cout):
-        lib = _native.load()
         qk, v, cqk, cv, out, cout, ws = ctx.saved_tensors
         mask, cmask = ctx.masks
         B, I, J = int(qk.shape[0]), int(qk.shape[1]), int(cqk.shape[1])
         d_out, d_cout = d_out.contiguous(), d_cout.contiguous()
         grads = [torch.empty_like(t) for t in (qk, v, cqk, cv)]
-        with torch.cuda.device(qk.device):
-            _native.check(lib.gsr_crossattn_backward(
-                B, ctx.heads, I, J, HIP_DIM_HEAD, _native.ptr(qk), _native.ptr(v), _native.ptr(cqk), _native.ptr(cv), _native.ptr(mask),
-                _native.ptr(cmask), ctx.scale, _native.ptr(out), _native.ptr(cout), _native.ptr(d_out), _native.ptr(d_cout),
-                _native.ptr(ws), _native.ptr(grads[0]), _native.ptr(grads[1]), _native.ptr(grads[2]), _native.ptr(grads[3]),
-                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_crossattn_backward")
+        _native.run(
+            "gsr_crossattn_backward", qk.device,
+            B, ctx.heads, I, J, HIP_DIM_HEAD, _native.ptr(qk), _native.ptr(v), _native.ptr(cqk), _native.ptr(cv), _native.ptr(mask),
+            _native.ptr(cmask), ctx.scale, _native.ptr(out), _native.ptr(cout), _native.ptr(d_out), _native.ptr(d_cout),
+            _native.ptr(ws), _native.ptr(grads[0]), _native.ptr(grads[1]), _native.ptr(grads[2]), _native.ptr(grads[3]))
         return grads[0], grads[1], grads[2], grads[3], None, None, None, None
 
 

@@ -62,7 +62,7 @@ struct GsrStageTimer {
 };
 
 // debug semantics of the reference's CHECK_CUDA (auxiliary.h:166-173): sync + check after a stage
-#define GSR_STAGE(stage_id, expr, what)                              \
+#define GSR_STAGE(stage_id, stream, debug, expr, what)               \
     do {                                                             \
         {                                                            \
             GsrStageTimer timer_(stage_id, stream);                  \
@@ -148,29 +148,48 @@ static bool gsr_occlusion(const gsr_tuning* tuning, int T)
     return tuning && tuning->occlusion_cut && !tuning->disable_tile_cull && T <= GSR_OCC_MAX_TILES;
 }
 
-static int gsr_make_cam(GsrCam& cam, int W, int H, const float* view_d, const float* proj_d, const float* campos_d,
-                        float tan_fovx, float tan_fovy, float scale_modifier, hipStream_t stream)
+static GsrCam gsr_make_cam(int W, int H, const float* view_d, const float* proj_d, const float* campos_d, float tan_fovx,
+                           float tan_fovy, float scale_modifier)
 {
-    (void)stream;
+    GsrCam cam;
     cam.view = view_d; cam.proj = proj_d; cam.campos = campos_d;
     cam.tan_fovx = tan_fovx; cam.tan_fovy = tan_fovy;
     cam.focal_y = H / (2.0f * tan_fovy);  // DGR rasterizer_impl.cu:226-227
     cam.focal_x = W / (2.0f * tan_fovx);
     cam.scale_modifier = scale_modifier;
     cam.W = W; cam.H = H;
-    cam.gx = (W + GSR_TILE - 1) / GSR_TILE; cam.gy = (H + GSR_TILE - 1) / GSR_TILE;
-    return GSR_OK;
+    const GsrGrid grid = gsr_tile_grid(W, H);
+    cam.gx = grid.gx; cam.gy = grid.gy;
+    return cam;
 }
 
 static int gsr_check_dims(int P, int W, int H)
 {
     if (P < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "P must be >= 0 (got %d)", P);
     if (W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image size must be positive (got %dx%d)", W, H);
-    const long gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
+    const GsrGrid grid = gsr_tile_grid(W, H);
+    const long gx = grid.gx, gy = grid.gy;
     if (gx > 65535 || gy > 65535) return gsr_fail(GSR_ERR_UNSUPPORTED, "image too large: %ldx%ld tiles", gx, gy);
     // more than GSR_MAX_TILES_LDS tiles: supported through the global-counter binning fallback (binning.hip)
     if (gx * gy > (1L << 24)) return gsr_fail(GSR_ERR_UNSUPPORTED, "image too large: %ld tiles", gx * gy);
     return GSR_OK;
+}
+
+// The frame of one entry point: the only place (besides the *_bytes queries) that carves the caller's workspaces.  Pointers are not
+// checked here -- carving a NULL workspace yields pointers nobody follows, the entry points report it -- and an entry point without
+// a binning workspace (stage 1) leaves `bin` / `capacity` unset.
+static GsrFrame gsr_make_frame(int P, int W, int H, const void* geom_ws, const void* image_ws, const void* binning_ws, int capacity,
+                               int debug, hipStream_t stream)
+{
+    GsrFrame f{};
+    const GsrGrid grid = gsr_tile_grid(W, H);
+    f.P = P; f.W = W; f.H = H;
+    f.gx = grid.gx; f.gy = grid.gy; f.T = grid.gx * grid.gy;
+    f.geom = gsr_carve_geom(const_cast<void*>(geom_ws), P);
+    f.image = gsr_carve_image(const_cast<void*>(image_ws), P, W, H);
+    if (binning_ws) { f.bin = gsr_carve_binning(const_cast<void*>(binning_ws), capacity); f.capacity = capacity; }
+    f.stream = stream; f.debug = debug;
+    return f;
 }
 
 // Per host thread and device: the pinned, device-mapped words the tile-scan kernel writes {R, longest list} into (valid
@@ -178,35 +197,31 @@ static int gsr_check_dims(int P, int W, int H)
 // alternates between devices finds each device's pair again (nothing is re-allocated on a switch); the pairs live as
 // long as the thread and are released when it exits.
 #define GSR_MAX_DEVICES 64
-struct GsrThreadDeviceState {
-    uint32_t* host[GSR_MAX_DEVICES] = {};
-    uint32_t* dev[GSR_MAX_DEVICES] = {};
-    hipEvent_t ev[GSR_MAX_DEVICES] = {};
-    uint8_t heavy_mode[GSR_MAX_DEVICES] = {};   // per-Gaussian backward: 1 = launch the heavy-group kernel (gsr_heavy_groups_expected)
-    uint8_t heavy_probe[GSR_MAX_DEVICES] = {};  // backwards to wait before the heavy kernel is launched again just to count the groups
+struct GsrDeviceState {
+    volatile uint32_t* host = nullptr;  // the pinned block (16 words, indices below) ...
+    uint32_t* dev = nullptr;            // ... and its address on the device
+    hipEvent_t ev = nullptr;            // created by the first gsr_forward
+    uint8_t heavy_mode = 0;   // per-Gaussian backward: 1 = launch the heavy-group kernel (gsr_heavy_groups_expected)
+    uint8_t heavy_probe = 0;  // backwards to wait before the heavy kernel is launched again just to count the groups
     // partial sort of long tile lists, the bet and its feedback (gsr_partial_bet)
-    uint32_t fwd_serial[GSR_MAX_DEVICES] = {};   // forwards of this thread on the device (what a resumed quadrant reports back)
-    uint32_t ranoff_seen[GSR_MAX_DEVICES] = {};  // the last report acted upon
-    uint8_t bet_hold[GSR_MAX_DEVICES] = {};      // forwards left during which lists up to GSR_SORT_CAP_SMALL are sorted completely at once
-    ~GsrThreadDeviceState()
+    uint32_t fwd_serial = 0;   // forwards of this thread on the device (what a resumed quadrant reports back)
+    uint32_t ranoff_seen = 0;  // the last report acted upon
+    uint8_t bet_hold = 0;      // forwards left during which lists up to GSR_SORT_CAP_SMALL are sorted completely at once
+};
+struct GsrThreadDevices {
+    GsrDeviceState of[GSR_MAX_DEVICES];
+    ~GsrThreadDevices()
     {
         for (int d = 0; d < GSR_MAX_DEVICES; d++) {
             // kernels of this thread's last calls may still store into the block (the heavy-group hint is written without a
             // host wait): drain the owning device before the block goes away
-            if (host[d] && hipSetDevice(d) == hipSuccess) (void)hipDeviceSynchronize();
-            if (host[d]) (void)hipHostFree(host[d]);
-            if (ev[d]) (void)hipEventDestroy(ev[d]);
+            if (of[d].host && hipSetDevice(d) == hipSuccess) (void)hipDeviceSynchronize();
+            if (of[d].host) (void)hipHostFree(const_cast<uint32_t*>(of[d].host));
+            if (of[d].ev) (void)hipEventDestroy(of[d].ev);
         }
     }
 };
-static thread_local GsrThreadDeviceState g_tds;
-
-static int gsr_current_device(int* d)
-{
-    GSR_HIP(hipGetDevice(d), "hipGetDevice");
-    if (*d < 0 || *d >= GSR_MAX_DEVICES) return gsr_fail(GSR_ERR_UNSUPPORTED, "device index %d out of range", *d);
-    return GSR_OK;
-}
+static thread_local GsrThreadDevices g_tds;
 
 // words of the pinned, device-mapped block (one per host thread and device): 0, 1 = {R, longest list} of stage 1, 4 = prefiltered
 // trap, 8 = the per-Gaussian backward's report on heavy groups (0 = nothing new, 1 = the one-wave kernel met one, 2 + n = the
@@ -216,20 +231,23 @@ static int gsr_current_device(int* d)
 #define GSR_PINNED_RANOFF 9
 #define GSR_BET_HOLD 64  // forwards without the partial sort after a lost bet, then one forward probes again
 #define GSR_HEAVY_MIN_GROUPS 192  // fewer heavy groups than this: the one-wave kernel does them itself (gauss_bwd.hip, launcher)
-static int gsr_info_buffer(volatile uint32_t** host, uint32_t** dev)
+
+// This thread's state on the current device; its pinned block is allocated at the first call.
+static int gsr_device_state(GsrDeviceState** state)
 {
     int d = 0;
-    int rc = gsr_current_device(&d);
-    if (rc) return rc;
-    if (!g_tds.host[d]) {
+    GSR_HIP(hipGetDevice(&d), "hipGetDevice");
+    if (d < 0 || d >= GSR_MAX_DEVICES) return gsr_fail(GSR_ERR_UNSUPPORTED, "device index %d out of range", d);
+    GsrDeviceState& s = g_tds.of[d];
+    if (!s.host) {
         void* p = nullptr;
         GSR_HIP(hipHostMalloc(&p, 64, hipHostMallocMapped), "hipHostMalloc(info)");
         void* pd = nullptr;
         GSR_HIP(hipHostGetDevicePointer(&pd, p, 0), "hipHostGetDevicePointer(info)");
         memset(p, 0, 64);
-        g_tds.host[d] = (uint32_t*)p; g_tds.dev[d] = (uint32_t*)pd;
+        s.host = (uint32_t*)p; s.dev = (uint32_t*)pd;
     }
-    *host = g_tds.host[d]; *dev = g_tds.dev[d];
+    *state = &s;
     return GSR_OK;
 }
 
@@ -256,108 +274,120 @@ static bool gsr_heavy_groups_expected(uint32_t report, uint8_t* mode, uint8_t* p
 // small LDS class (<= GSR_SORT_CAP_SMALL entries) completely at once -- one launch, no fix-up -- then one forward bets again.  Longer
 // lists always bet: a complete sort of 10 000-entry lists costs more than the fix-up.  Results never depend on any of this (the
 // partial sort is bit-identical to a complete one, tests + tools/fuzz_parity.py).  -> the partial sort is worth betting on
-static bool gsr_partial_bet(int devidx, const volatile uint32_t* pinned, int longest, bool longest_is_a_provision)
+static bool gsr_partial_bet(GsrDeviceState& s, int longest, bool longest_is_a_provision)
 {
-    const uint32_t rep = pinned[GSR_PINNED_RANOFF];
-    if (rep != g_tds.ranoff_seen[devidx]) { g_tds.ranoff_seen[devidx] = rep; g_tds.bet_hold[devidx] = GSR_BET_HOLD; }
-    const bool hold = g_tds.bet_hold[devidx] > 0;
-    if (hold) --g_tds.bet_hold[devidx];
+    const uint32_t rep = s.host[GSR_PINNED_RANOFF];
+    if (rep != s.ranoff_seen) { s.ranoff_seen = rep; s.bet_hold = GSR_BET_HOLD; }
+    const bool hold = s.bet_hold > 0;
+    if (hold) --s.bet_hold;
     // (a speculative caller provisions the longest list with slack over what its last frames had -- gsraster.h: 1.25 x: the call then
     // sorts completely up to GSR_SORT_CAP_SMALL and treats anything longer like any list beyond its provision: GSR_NEED_CAPACITY)
     const int limit = longest_is_a_provision ? GSR_SORT_CAP_SMALL + GSR_SORT_CAP_SMALL / 4 + 64 : GSR_SORT_CAP_SMALL;
     return !(hold && longest > GSR_NEAR_CAP && longest <= limit);
 }
 
+// One more forward of this thread on the current device that may sort partially: does it bet (gsr_partial_bet)?
+static int gsr_count_forward_and_bet(int longest, bool longest_is_a_provision, bool* bet)
+{
+    GsrDeviceState* s = nullptr;
+    const int rc = gsr_device_state(&s);
+    if (rc) return rc;
+    ++s->fwd_serial;
+    *bet = gsr_partial_bet(*s, longest, longest_is_a_provision);
+    return GSR_OK;
+}
+
 extern "C" void gsr_adaptive_reset(void)
 {
     // forget what this thread's previous calls taught the launch heuristics (tests, gscream_amd.set_tuning): reports that are
     // still on their way count as seen
-    for (int d = 0; d < GSR_MAX_DEVICES; d++) {
-        g_tds.bet_hold[d] = 0;
-        if (g_tds.host[d]) g_tds.ranoff_seen[d] = ((volatile uint32_t*)g_tds.host[d])[GSR_PINNED_RANOFF];
+    for (GsrDeviceState& s : g_tds.of) {
+        s.bet_hold = 0;
+        if (s.host) s.ranoff_seen = s.host[GSR_PINNED_RANOFF];
     }
-}
-
-static int gsr_info_event(hipEvent_t* ev)
-{
-    int d = 0;
-    int rc = gsr_current_device(&d);
-    if (rc) return rc;
-    if (!g_tds.ev[d]) GSR_HIP(hipEventCreateWithFlags(&g_tds.ev[d], hipEventDisableTiming), "hipEventCreate");
-    *ev = g_tds.ev[d];
-    return GSR_OK;
 }
 
 // `prefiltered` (GaussianRasterizationSettings field 11).  The reference uses it for one thing: a point that fails the near
 // plane although the caller declared the cloud pre-filtered prints "Point is filtered although prefiltered is set" and
 // traps the kernel (DGR auxiliary.h:154-162) -- the process then dies at its next synchronisation.  Here the same
 // condition is an ordinary error of the call, checked in debug mode (`debug=True` synchronises after every stage anyway);
-// without debug the flag costs nothing and culled points are simply culled.
+// without debug the flag costs nothing and culled points are simply culled.  (Missing pointers are left to the argument
+// checks that follow in the forward entry points.)
 static int gsr_prefiltered_trap(int P, int prefiltered, int debug, const float* means3D, const float* viewmatrix, hipStream_t stream)
 {
-    if (!prefiltered || !debug || P <= 0) return GSR_OK;
-    volatile uint32_t* host = nullptr;
-    uint32_t* dev = nullptr;
-    int rc = gsr_info_buffer(&host, &dev);
+    if (!prefiltered || !debug || P <= 0 || !means3D || !viewmatrix) return GSR_OK;
+    GsrDeviceState* s = nullptr;
+    int rc = gsr_device_state(&s);
     if (rc) return rc;
     GSR_HIP(hipStreamSynchronize(stream), "prefiltered check");  // nothing in flight may still write the info words
-    host[4] = 0u;
-    GSR_HIP(gsr_launch_prefiltered_check(P, means3D, viewmatrix, dev + 4, stream), "prefiltered check");
+    s->host[4] = 0u;
+    GSR_HIP(gsr_launch_prefiltered_check(P, means3D, viewmatrix, s->dev + 4, stream), "prefiltered check");
     GSR_HIP(hipStreamSynchronize(stream), "prefiltered check");
-    const uint32_t n = host[4];
+    const uint32_t n = s->host[4];
     if (n) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "Point is filtered although prefiltered is set. This shouldn't happen! "
                                                     "(%u of %d points have view-space z <= 0.2)", n, P);
     return GSR_OK;
 }
 
-// Validates the stage-1 arguments and enqueues preprocess + counting + the 16-byte D2H copy of {R, max tile count}.
-static int gsr_enqueue_stage1(int P, int D, int M, int W, int H, const float* means3D, const float* scales,
+// The opening gsr_forward and gsr_forward_stage1 share.  *empty: there is nothing to render, the call is over (result zeroed).
+static int gsr_open_forward(int P, int W, int H, int prefiltered, int debug, const float* means3D, const float* viewmatrix,
+                            gsr_stage1_result* result_host, hipStream_t stream, bool* empty)
+{
+    *empty = true;
+    const int rc = gsr_check_dims(P, W, H);
+    if (rc) return rc;
+    if (!result_host) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "result_host is NULL");
+    memset(result_host, 0, sizeof(*result_host));
+    if (P == 0) return GSR_OK;  // DGR rasterize_points.cu:85
+    *empty = false;
+    return gsr_prefiltered_trap(P, prefiltered, debug, means3D, viewmatrix, stream);
+}
+
+// Validates the stage-1 arguments and enqueues preprocess + counting; *state: where the scan kernel's {R, longest list} arrive.
+static int gsr_enqueue_stage1(const GsrFrame& f, int D, int M, const float* means3D, const float* scales,
                               float scale_modifier, const float* rotations, const float* opacities,
                               const float* features, const float* shs, const float* cov3D_precomp,
                               const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
-                              const float* campos, float tan_fovx, float tan_fovy, void* geom_ws, void* image_ws,
-                              int32_t* radii, volatile uint32_t** info_pinned, uint32_t** info_mapped_dev, bool defer_tile_scan,
-                              const gsr_tuning* tuning, bool* ordered /* out (or NULL): the forward blend's dispatch order was computed
-                              beside the column scan (gsr_tuning.walk_depths) */, int debug, hipStream_t stream)
+                              const float* campos, float tan_fovx, float tan_fovy, int32_t* radii, GsrDeviceState** state,
+                              bool defer_tile_scan, const gsr_tuning* tuning,
+                              bool* ordered /* out (or NULL): the forward blend's dispatch order was computed beside the column scan
+                              (gsr_tuning.walk_depths) */)
 {
-    if (!means3D || !opacities || !features || !viewmatrix || !projmatrix || !geom_ws || !image_ws || !radii)
+    // (geom.rec and image.ranges are the first things carved: the workspace pointers themselves)
+    if (!means3D || !opacities || !features || !viewmatrix || !projmatrix || !f.geom.rec || !f.image.ranges || !radii)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "a required pointer is NULL");
     if ((!scales || !rotations) == (cov3D_precomp == nullptr))  // DGR __init__.py:227-228
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "provide exactly one of scales+rotations or cov3D_precomp");
     if ((shs == nullptr) == (colors_precomp == nullptr))  // DGR __init__.py:224-225
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "provide exactly one of shs or colors_precomp");
     if (shs && (!campos || M <= 0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "SH colours need campos and M > 0");
-    GsrCam cam;
-    int rc = gsr_make_cam(cam, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, stream);
-    if (rc) return rc;
-    const GsrGeom geom = gsr_carve_geom(geom_ws, P);
-    const GsrImage image = gsr_carve_image(image_ws, P, W, H);
-    const int T = cam.gx * cam.gy;
-    const bool occlusion = gsr_occlusion(tuning, T);
-    if (occlusion) GSR_HIP(hipMemsetAsync(image.occ_mass, 0, (size_t)GSR_OCC_COPIES * T * GSR_OCC_BUCKETS * sizeof(uint32_t), stream), "clear occlusion masses");
-    GSR_STAGE(GSR_STAGE_PREPROCESS, gsr_launch_preprocess(0, P, D, M, cam, means3D, scales, rotations, opacities, features, shs,
-                                    cov3D_precomp, colors_precomp, &geom, radii, nullptr, nullptr,
-                                    !(tuning && tuning->disable_tile_cull), occlusion ? image.occ_mass : nullptr, stream),
+    const GsrCam cam = gsr_make_cam(f.W, f.H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier);
+    const bool occlusion = gsr_occlusion(tuning, f.T);
+    if (occlusion) GSR_HIP(hipMemsetAsync(f.image.occ_mass, 0, (size_t)GSR_OCC_COPIES * f.T * GSR_OCC_BUCKETS * sizeof(uint32_t), f.stream), "clear occlusion masses");
+    GSR_STAGE(GSR_STAGE_PREPROCESS, f.stream, f.debug,
+              gsr_launch_preprocess(0, f.P, D, M, cam, means3D, scales, rotations, opacities, features, shs, cov3D_precomp, colors_precomp,
+                                    &f.geom, radii, nullptr, nullptr, !(tuning && tuning->disable_tile_cull),
+                                    occlusion ? f.image.occ_mass : nullptr, f.stream),
               "preprocess");
     // {R, longest list} reach the host through a pinned, device-mapped word pair the scan kernel stores into (one per
     // host thread and device, 8 bytes, kept for the life of the thread): no copy kernel between the scan and the scatter.
-    uint32_t* mapped_dev = nullptr;
-    rc = gsr_info_buffer(info_pinned, &mapped_dev);
+    const int rc = gsr_device_state(state);
     if (rc) return rc;
-    if (info_mapped_dev) *info_mapped_dev = mapped_dev;
     const GsrWalkHint walk = gsr_walk_hint(tuning);
-    GSR_STAGE(GSR_STAGE_COUNT_SCAN, gsr_launch_count(P, T, cam.gx, geom, image, mapped_dev, defer_tile_scan, occlusion,
-                                                     (ordered && walk.valid) ? walk.depths : nullptr, ordered, stream), "tile count / scans");
+    GSR_STAGE(GSR_STAGE_COUNT_SCAN, f.stream, f.debug,
+              gsr_launch_count(f, (*state)->dev, defer_tile_scan, occlusion, (ordered && walk.valid) ? walk.depths : nullptr, ordered),
+              "tile count / scans");
     return GSR_OK;
 }
 
-static int gsr_publish_stage1(const uint32_t* info, gsr_stage1_result* out)
+static int gsr_publish_stage1(const volatile uint32_t* info, gsr_stage1_result* out)
 {
-    if (info[0] > 0x7fffffffu) return gsr_fail(GSR_ERR_UNSUPPORTED, "instance count %u overflows int32", info[0]);
-    out->num_rendered = (int32_t)info[0];
-    out->max_tile_count = (int32_t)info[1];
-    out->num_slots = (int32_t)info[0];  // one gradient slot per binned instance
-    out->num_occluded = (int32_t)info[2];
+    const uint32_t got[3] = { info[0], info[1], info[2] };
+    if (got[0] > 0x7fffffffu) return gsr_fail(GSR_ERR_UNSUPPORTED, "instance count %u overflows int32", got[0]);
+    out->num_rendered = (int32_t)got[0];
+    out->max_tile_count = (int32_t)got[1];
+    out->num_slots = (int32_t)got[0];  // one gradient slot per binned instance
+    out->num_occluded = (int32_t)got[2];
     return GSR_OK;
 }
 
@@ -370,74 +400,71 @@ extern "C" int gsr_forward_stage1(int P, int D, int M, int W, int H, const float
                                   const gsr_tuning* tuning, int debug, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = gsr_check_dims(P, W, H);
-    if (rc) return rc;
-    if (!result_host) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "result_host is NULL");
-    memset(result_host, 0, sizeof(*result_host));
-    if (P == 0) return GSR_OK;  // DGR rasterize_points.cu:85
-    if (prefiltered && debug && means3D && viewmatrix) {
-        rc = gsr_prefiltered_trap(P, prefiltered, debug, means3D, viewmatrix, stream);
-        if (rc) return rc;
-    }
-    volatile uint32_t* info = nullptr;  // pinned words the scan kernel writes {R, max} into
-    rc = gsr_enqueue_stage1(P, D, M, W, H, means3D, scales, scale_modifier, rotations, opacities, features, shs,
-                            cov3D_precomp, colors_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_ws,
-                            image_ws, radii, &info, nullptr, false, tuning, nullptr, debug, stream);
+    bool empty = false;
+    int rc = gsr_open_forward(P, W, H, prefiltered, debug, means3D, viewmatrix, result_host, stream, &empty);
+    if (rc || empty) return rc;
+    const GsrFrame f = gsr_make_frame(P, W, H, geom_ws, image_ws, nullptr, 0, debug, stream);
+    GsrDeviceState* state = nullptr;
+    rc = gsr_enqueue_stage1(f, D, M, means3D, scales, scale_modifier, rotations, opacities, features, shs, cov3D_precomp,
+                            colors_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, &state, false, tuning, nullptr);
     if (rc) return rc;
     GSR_HIP(hipStreamSynchronize(stream), "read num_rendered");
-    uint32_t got[3] = { info[0], info[1], info[2] };
-    return gsr_publish_stage1(got, result_host);
+    return gsr_publish_stage1(state->host, result_host);
 }
+
+// where a forward renders to
+struct GsrTargets { const float* background; float* color; float* depth; float* feature; };
 
 // After a forward over partially sorted lists (binning.hip): tiles whose pixels were still blending at the end of their
 // sorted prefix get a full sort and are blended again.  Nothing happens on the GPU beyond a few empty launches when no
 // tile asked for it; not enqueued at all when no list was long enough to be partially sorted.
-static int gsr_enqueue_fixup(int P, int W, int H, int capacity, int max_tile_count, const float* background, void* geom_ws,
-                             void* image_ws, void* binning_ws, float* out_color, float* out_depth, float* out_feature,
-                             bool inference, GsrWalkHint walk, int debug, hipStream_t stream)
+static int gsr_enqueue_fixup(const GsrFrame& f, int max_tile_count, const GsrTargets& to, bool inference, GsrWalkHint walk)
 {
     if (max_tile_count <= GSR_NEAR_CAP) return GSR_OK;
-    // where a resumed quadrant reports the lost bet (gsr_partial_bet)
-    volatile uint32_t* pinned = nullptr;
-    uint32_t* pinned_dev = nullptr;
-    int devidx = 0;
-    int rc0 = gsr_info_buffer(&pinned, &pinned_dev);
-    if (rc0) return rc0;
-    rc0 = gsr_current_device(&devidx);
-    if (rc0) return rc0;
-    const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE, T = gx * gy;
-    const GsrGeom geom = gsr_carve_geom(geom_ws, P);
-    const GsrImage image = gsr_carve_image(image_ws, P, W, H);
-    const GsrBinning bin = gsr_carve_binning(binning_ws, capacity);
-    GSR_STAGE(GSR_STAGE_TILE_SORT, gsr_launch_sort_fixup(T, capacity, max_tile_count, image, bin, inference, stream), "tile sort (fix-up)");
-    GSR_STAGE(GSR_STAGE_BLEND_FWD, gsr_launch_blend_forward(W, H, gx, T, background, geom, image, bin, out_color, out_depth,
-                                                            out_feature, capacity, max_tile_count, true, inference, walk.depths, walk.valid, false,
-                                                            pinned_dev + GSR_PINNED_RANOFF, g_tds.fwd_serial[devidx], stream),
-              "forward blend (fix-up)");
+    GsrDeviceState* s = nullptr;
+    const int rc = gsr_device_state(&s);
+    if (rc) return rc;
+    GSR_STAGE(GSR_STAGE_TILE_SORT, f.stream, f.debug, gsr_launch_sort_fixup(f, max_tile_count, inference), "tile sort (fix-up)");
+    GsrBlendPass pass{};
+    pass.only_flagged = true;
+    pass.inference = inference;
+    pass.walk_depths = walk.depths;
+    pass.walk_depths_valid = walk.valid;
+    pass.ranoff_report = s->dev + GSR_PINNED_RANOFF;  // where a resumed quadrant reports the lost bet (gsr_partial_bet)
+    pass.serial = s->fwd_serial;
+    GSR_STAGE(GSR_STAGE_BLEND_FWD, f.stream, f.debug,
+              gsr_launch_blend_forward(f, to.background, to.color, to.depth, to.feature, max_tile_count, pass), "forward blend (fix-up)");
     return GSR_OK;
 }
 
-static int gsr_enqueue_stage2(int P, int W, int H, int capacity, int max_tile_count, int partial /* gsr_launch_tile_sort */, bool inference, int forced_bands, const float* background,
-                              void* geom_ws, void* image_ws, void* binning_ws, float* out_color, float* out_depth,
-                              float* out_feature, GsrWalkHint walk, int debug, hipStream_t stream)
+// Stage 2 -- scatter, tile sort, forward blend -- in its two forms, told apart by `scattered`:
+//   exact (gsr_forward_stage2, `scattered` NULL): R and the longest list are known; `longest` is the longest list.
+//   speculative (gsr_forward, `scattered` = the thread's event): enqueued BEFORE the host waits for R, so the GPU never idles on
+//     the host round trip the reference pays at rasterizer_impl.cu:287; `longest` is the caller's hint (-1: none), which chooses
+//     the sort variants -- with partial sorting it only sizes the LDS of the lists up to GSR_NEAR_CAP.  The event is recorded
+//     behind the scatter, whose kernel stores {R, longest list} (scatter.fused_tile_scan; beyond the LDS tile limit stage 1 ran
+//     the stand-alone tile scan: the same words, written earlier).
+static int gsr_enqueue_stage2(const GsrFrame& f, hipEvent_t scattered, int longest, int sort_mode /* gsr_launch_tile_sort */,
+                              const GsrScatterPass& scatter, bool ordered, GsrWalkHint walk, const GsrTargets& to)
 {
-    const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE, T = gx * gy;
-    const GsrGeom geom = gsr_carve_geom(geom_ws, P);
-    const GsrImage image = gsr_carve_image(image_ws, P, W, H);
-    const GsrBinning bin = gsr_carve_binning(binning_ws, capacity);
+    const bool speculative = scattered != nullptr;
     // info[3] (quadrant walks that entered the second depth tier) is zeroed by the tile scan of stage 1 and counted up by the forward
     // blend: a stage 2 that REPEATS a speculative forward (GSR_NEED_CAPACITY) would count those walks twice and could flip the
     // backward's launch order on exactly the frames that outgrew their hint (results never depended on it)
-    GSR_HIP(hipMemsetAsync(image.info + 3, 0, sizeof(uint32_t), stream), "reset the deep-walk counter");
-    GSR_STAGE(GSR_STAGE_SCATTER, gsr_launch_scatter(P, T, gx, geom, image, bin, capacity, capacity, forced_bands, false, nullptr, inference, false, stream), "scatter");
-    GSR_STAGE(GSR_STAGE_TILE_SORT, gsr_launch_tile_sort(T, capacity, max_tile_count, partial, false, inference, geom, image, bin, stream), "tile sort");
-    GSR_STAGE(GSR_STAGE_BLEND_FWD, gsr_launch_blend_forward(W, H, gx, T, background, geom, image, bin, out_color, out_depth,
-                                                            out_feature, capacity, max_tile_count, false, inference, walk.depths, walk.valid, false, nullptr, 0u, stream),
-              "forward blend");
-    // longest list known (two-stage form): the fix-up can follow at once; the one-call form enqueues it after the read-back
-    if (partial == 1 && max_tile_count >= 0)
-        return gsr_enqueue_fixup(P, W, H, capacity, max_tile_count, background, geom_ws, image_ws, binning_ws, out_color,
-                                 out_depth, out_feature, inference, walk, debug, stream);
+    if (!speculative) GSR_HIP(hipMemsetAsync(f.image.info + 3, 0, sizeof(uint32_t), f.stream), "reset the deep-walk counter");
+    GSR_STAGE(GSR_STAGE_SCATTER, f.stream, f.debug, gsr_launch_scatter(f, scatter), "scatter");
+    if (speculative) GSR_HIP(hipEventRecord(scattered, f.stream), "record");
+    // sort mode 1: lists beyond GSR_NEAR_CAP take the fixed-LDS prefix sort whatever `longest` says
+    GSR_STAGE(GSR_STAGE_TILE_SORT, f.stream, f.debug, gsr_launch_tile_sort(f, longest, sort_mode, speculative, scatter.inference), "tile sort");
+    GsrBlendPass pass{};
+    pass.inference = scatter.inference;
+    pass.walk_depths = walk.depths;
+    pass.walk_depths_valid = walk.valid;
+    pass.already_ordered = ordered;
+    GSR_STAGE(GSR_STAGE_BLEND_FWD, f.stream, f.debug,
+              gsr_launch_blend_forward(f, to.background, to.color, to.depth, to.feature, longest, pass), "forward blend");
+    // longest list known (exact form): the fix-up can follow at once; the speculative form enqueues it after the read-back
+    if (!speculative && sort_mode == 1 && longest >= 0) return gsr_enqueue_fixup(f, longest, to, scatter.inference, walk);
     return GSR_OK;
 }
 
@@ -451,77 +478,47 @@ extern "C" int gsr_forward(int P, int D, int M, int W, int H, const float* means
                            const gsr_tuning* tuning, int debug, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = gsr_check_dims(P, W, H);
-    if (rc) return rc;
-    if (!result_host) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "result_host is NULL");
-    memset(result_host, 0, sizeof(*result_host));
-    if (P == 0) return GSR_OK;
-    if (prefiltered && debug && means3D && viewmatrix) {
-        rc = gsr_prefiltered_trap(P, prefiltered, debug, means3D, viewmatrix, stream);
-        if (rc) return rc;
-    }
+    bool empty = false;
+    int rc = gsr_open_forward(P, W, H, prefiltered, debug, means3D, viewmatrix, result_host, stream, &empty);
+    if (rc || empty) return rc;
     if (!background || !binning_ws || !out_color || !out_depth || !out_feature || binning_capacity <= 0)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "a required pointer is NULL or the binning capacity is not positive");
-    // One event per thread and device marks "R is on the host"; stage 2 is enqueued BEFORE we wait for it, so the GPU
-    // never idles on the host round trip the reference pays at rasterizer_impl.cu:287.
-    hipEvent_t ev = nullptr;
-    rc = gsr_info_event(&ev);
-    if (rc) return rc;
-    volatile uint32_t* info = nullptr;
-    uint32_t* info_dev = nullptr;
+    const GsrFrame f = gsr_make_frame(P, W, H, geom_ws, image_ws, binning_ws, binning_capacity, debug, stream);
+    const GsrTargets to = { background, out_color, out_depth, out_feature };
     // The tile scan (ranges, R, longest list) is folded into the scatter kernel here: nobody needs R before stage 2 is
     // enqueued, and the one-block launch cost as much as the whole column scan.  The event therefore follows the scatter.
-    // the caller provisions the workspace with slack over what it expects (gsraster.h: "e.g. 1.25 x the previous frame's
-    // num_rendered"): the scatter's staging (and its bands, binning.hip) is sized for the expectation, not for the provision
-    const int expected_R = (int)(0.8 * (double)binning_capacity);
-    const bool fold_tile_scan = true;
+    GsrDeviceState* state = nullptr;
     bool ordered = false;
-    rc = gsr_enqueue_stage1(P, D, M, W, H, means3D, scales, scale_modifier, rotations, opacities, features, shs,
-                            cov3D_precomp, colors_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_ws,
-                            image_ws, radii, &info, &info_dev, fold_tile_scan, tuning, &ordered, debug, stream);
+    rc = gsr_enqueue_stage1(f, D, M, means3D, scales, scale_modifier, rotations, opacities, features, shs, cov3D_precomp,
+                            colors_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, &state, true, tuning, &ordered);
     if (rc) return rc;
+    // One event per thread and device marks "R is on the host" (created at the thread's first forward on the device)
+    if (!state->ev) GSR_HIP(hipEventCreateWithFlags(&state->ev, hipEventDisableTiming), "hipEventCreate");
     bool partial = gsr_partial_sort(tuning);
     int sort_mode = partial ? 1 : 0;
-    const bool inference = gsr_inference(tuning);
     if (partial) {  // ... unless this thread's recent forwards lost the bet on lists like these (gsr_partial_bet)
-        volatile uint32_t* pinned = nullptr;
-        uint32_t* pinned_dev = nullptr;
-        int devidx = 0;
-        rc = gsr_info_buffer(&pinned, &pinned_dev);
+        rc = gsr_count_forward_and_bet(max_tile_count_hint, true, &partial);
         if (rc) return rc;
-        rc = gsr_current_device(&devidx);
-        if (rc) return rc;
-        ++g_tds.fwd_serial[devidx];
-        partial = gsr_partial_bet(devidx, pinned, max_tile_count_hint, true);
         if (!partial) {  // complete sorts, the few long lists in a launch of their own, nothing beyond the small LDS class
             sort_mode = 2;
             if (max_tile_count_hint > GSR_SORT_CAP_SMALL) max_tile_count_hint = GSR_SORT_CAP_SMALL;
         }
     }
+    const bool inference = gsr_inference(tuning);
     const GsrWalkHint walk = gsr_walk_hint(tuning);
-    // (speculative: the sort variants are chosen from the hint; with partial sorting the hint only sizes the LDS of the
-    // lists up to GSR_NEAR_CAP)
-    {
-        const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE, T = gx * gy;
-        const GsrGeom geom = gsr_carve_geom(geom_ws, P);
-        const GsrImage image = gsr_carve_image(image_ws, P, W, H);
-        const GsrBinning bin = gsr_carve_binning(binning_ws, binning_capacity);
-        const int hint = max_tile_count_hint > 0 ? max_tile_count_hint : -1;
-        GSR_STAGE(GSR_STAGE_SCATTER, gsr_launch_scatter(P, T, gx, geom, image, bin, binning_capacity, expected_R, gsr_forced_bands(tuning), true, info_dev, inference,
-                                                        gsr_occlusion(tuning, T), stream), "scatter");
-        // (beyond the LDS tile limit stage 1 ran the stand-alone tile scan: the same words, written earlier)
-        GSR_HIP(hipEventRecord(ev, stream), "record");
-        // partial: lists beyond GSR_NEAR_CAP take the fixed-LDS prefix sort whatever the hint says
-        GSR_STAGE(GSR_STAGE_TILE_SORT, gsr_launch_tile_sort(T, binning_capacity, hint, sort_mode, true, inference, geom, image, bin, stream),
-                  "tile sort");
-        GSR_STAGE(GSR_STAGE_BLEND_FWD, gsr_launch_blend_forward(W, H, gx, T, background, geom, image, bin, out_color, out_depth,
-                                                                out_feature, binning_capacity, hint, false, inference, walk.depths, walk.valid, ordered, nullptr, 0u, stream),
-                  "forward blend");
-    }
+    GsrScatterPass scatter{};
+    // the caller provisions the workspace with slack over what it expects (gsraster.h: "e.g. 1.25 x the previous frame's
+    // num_rendered"): the scatter's staging (and its bands, binning.hip) is sized for the expectation, not for the provision
+    scatter.expected_instances = (int)(0.8 * (double)binning_capacity);
+    scatter.forced_bands = gsr_forced_bands(tuning);
+    scatter.fused_tile_scan = true;
+    scatter.fused_info_host = state->dev;
+    scatter.inference = inference;
+    scatter.occlusion_cut = gsr_occlusion(tuning, f.T);
+    rc = gsr_enqueue_stage2(f, state->ev, max_tile_count_hint > 0 ? max_tile_count_hint : -1, sort_mode, scatter, ordered, walk, to);
     if (rc) return rc;
-    GSR_HIP(hipEventSynchronize(ev), "read num_rendered");
-    uint32_t got[3] = { info[0], info[1], info[2] };
-    rc = gsr_publish_stage1(got, result_host);
+    GSR_HIP(hipEventSynchronize(state->ev), "read num_rendered");
+    rc = gsr_publish_stage1(state->host, result_host);
     if (rc) return rc;
     // the guesses hold iff every list fitted the workspace AND the sort variants that were launched cover the longest list
     const bool ok = result_host->num_rendered <= binning_capacity &&
@@ -529,9 +526,7 @@ extern "C" int gsr_forward(int P, int D, int M, int W, int H, const float* means
                      (partial && max_tile_count_hint > GSR_NEAR_CAP));  // lists beyond the cap do not depend on the hint
     // (strictly greater: gsr_launch_tile_sort starts the prefix-sort kernel only for a provision > GSR_NEAR_CAP)
     if (!ok) return GSR_NEED_CAPACITY;
-    if (partial)
-        return gsr_enqueue_fixup(P, W, H, binning_capacity, result_host->max_tile_count, background, geom_ws, image_ws,
-                                 binning_ws, out_color, out_depth, out_feature, inference, walk, debug, stream);
+    if (partial) return gsr_enqueue_fixup(f, result_host->max_tile_count, to, inference, walk);
     return GSR_OK;
 }
 
@@ -539,27 +534,26 @@ extern "C" int gsr_forward_stage2(int P, int W, int H, int R, int max_tile_count
                                   void* geom_ws, void* image_ws, void* binning_ws, float* out_color, float* out_depth,
                                   float* out_feature, const gsr_tuning* tuning, int debug, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     int rc = gsr_check_dims(P, W, H);
     if (rc) return rc;
     if (P == 0) return GSR_OK;  // outputs keep the caller's zero fill, like DGR rasterize_points.cu:69-85
     if (!background || !geom_ws || !image_ws || !binning_ws || !out_color || !out_depth || !out_feature)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "a required pointer is NULL");
     if (R < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "R must be >= 0");
-    bool partial = gsr_partial_sort(tuning);
-    if (partial) {  // (gsr_partial_bet: not when this thread's recent forwards lost the bet on lists like these)
-        volatile uint32_t* pinned = nullptr;
-        uint32_t* pinned_dev = nullptr;
-        int devidx = 0;
-        rc = gsr_info_buffer(&pinned, &pinned_dev);
+    int sort_mode = 0;
+    if (gsr_partial_sort(tuning)) {  // (gsr_partial_bet: not when this thread's recent forwards lost the bet on lists like these)
+        bool bet = false;
+        rc = gsr_count_forward_and_bet(max_tile_count, false, &bet);
         if (rc) return rc;
-        rc = gsr_current_device(&devidx);
-        if (rc) return rc;
-        ++g_tds.fwd_serial[devidx];
-        partial = gsr_partial_bet(devidx, pinned, max_tile_count, false);
+        sort_mode = bet ? 1 : 2;
     }
-    return gsr_enqueue_stage2(P, W, H, R, max_tile_count, partial ? 1 : gsr_partial_sort(tuning) ? 2 : 0, gsr_inference(tuning), gsr_forced_bands(tuning), background, geom_ws, image_ws, binning_ws,
-                              out_color, out_depth, out_feature, gsr_walk_hint(tuning), debug, stream);
+    const GsrFrame f = gsr_make_frame(P, W, H, geom_ws, image_ws, binning_ws, R, debug, (hipStream_t)stream_);
+    GsrScatterPass scatter{};
+    scatter.expected_instances = R;
+    scatter.forced_bands = gsr_forced_bands(tuning);
+    scatter.inference = gsr_inference(tuning);
+    return gsr_enqueue_stage2(f, nullptr, max_tile_count, sort_mode, scatter, false, gsr_walk_hint(tuning),
+                              GsrTargets{ background, out_color, out_depth, out_feature });
 }
 
 extern "C" int gsr_backward(int P, int D, int M, int W, int H, int R, int binning_capacity, int max_tile_count, const float* background,
@@ -589,24 +583,20 @@ extern "C" int gsr_backward(int P, int D, int M, int W, int H, int R, int binnin
     if (shs && (!dL_dsh || !campos || M <= 0))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "SH colours need dL_dsh, campos and M > 0");
     if (R < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "R must be >= 0");
-
-    GsrCam cam;
-    rc = gsr_make_cam(cam, W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, stream);
-    if (rc) return rc;
-    const int T = cam.gx * cam.gy;
-    const GsrGeom geom = gsr_carve_geom(const_cast<void*>(geom_ws), P);
-    const GsrImage image = gsr_carve_image(const_cast<void*>(image_ws), P, W, H);
     if (binning_capacity < R) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "binning_capacity < R");
-    const GsrBinning bin = gsr_carve_binning(const_cast<void*>(binning_ws), binning_capacity);
+
+    const GsrCam cam = gsr_make_cam(W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier);
+    const GsrFrame f = gsr_make_frame(P, W, H, geom_ws, image_ws, binning_ws, binning_capacity, debug, stream);
     float* slots = (float*)scratch;
     // heavy[0] = number of heavy groups (zeroed by the backward blend, which always runs first), heavy[16..] = their indices
     uint32_t* heavy = (uint32_t*)((char*)scratch + gsr_align((size_t)(R > 0 ? R : 1) * GSR_SLOT_FLOATS * sizeof(float)));
     // written-slot flags: cleared by the forward's tile sort, set by the backward blend; the set of written slots is a function
     // of the forward state alone, so a second backward over the same forward state finds exactly the flags it would set
-    uint8_t* slot_written = bin.slot_written;
+    uint8_t* slot_written = f.bin.slot_written;
     if (R > 0)
-        GSR_STAGE(GSR_STAGE_BLEND_BWD, gsr_launch_blend_backward(W, H, cam.gx, T, background, geom, image, bin, dL_dout_color, dL_dout_depth,
-                                            dL_dout_feature, slots, slot_written, heavy, max_tile_count > 0 ? max_tile_count : -1, stream),
+        GSR_STAGE(GSR_STAGE_BLEND_BWD, stream, debug,
+                  gsr_launch_blend_backward(f, background, dL_dout_color, dL_dout_depth, dL_dout_feature, slots, slot_written, heavy,
+                                            max_tile_count > 0 ? max_tile_count : -1),
                   "backward blend");
     else
         GSR_HIP(hipMemsetAsync(heavy, 0, 2 * sizeof(uint32_t), stream), "heavy-group counters");
@@ -614,18 +604,15 @@ extern "C" int gsr_backward(int P, int D, int M, int W, int H, int R, int binnin
     // through one word of the pinned block, read and cleared here without waiting for anything -- a hint only: both ways give the
     // same bits.  The heavy kernel reports how many groups it was given; below GSR_HEAVY_MIN_GROUPS the next calls go without it
     // (then only "met one" is known, so every 64th call launches it again to count).
-    volatile uint32_t* pinned = nullptr;
-    uint32_t* pinned_dev = nullptr;
-    rc = gsr_info_buffer(&pinned, &pinned_dev);
+    GsrDeviceState* state = nullptr;
+    rc = gsr_device_state(&state);
     if (rc) return rc;
-    int devidx = 0;
-    rc = gsr_current_device(&devidx);
-    if (rc) return rc;
-    bool heavy_expected = gsr_heavy_groups_expected(pinned[GSR_PINNED_HEAVY_SEEN], &g_tds.heavy_mode[devidx], &g_tds.heavy_probe[devidx]);
+    bool heavy_expected = gsr_heavy_groups_expected(state->host[GSR_PINNED_HEAVY_SEEN], &state->heavy_mode, &state->heavy_probe);
     if (tuning && tuning->heavy_groups) heavy_expected = tuning->heavy_groups == 1;
-    pinned[GSR_PINNED_HEAVY_SEEN] = 0u;
-    GSR_STAGE(GSR_STAGE_GAUSS_BWD, gsr_launch_gauss_backward(P, D, M, cam, means3D, radii, shs, scales, rotations, cov3D_precomp, geom, slots, slot_written, heavy,
-                                        pinned_dev + GSR_PINNED_HEAVY_SEEN, heavy_expected, R,
+    state->host[GSR_PINNED_HEAVY_SEEN] = 0u;
+    GSR_STAGE(GSR_STAGE_GAUSS_BWD, stream, debug,
+              gsr_launch_gauss_backward(P, D, M, cam, means3D, radii, shs, scales, rotations, cov3D_precomp, f.geom, slots, slot_written, heavy,
+                                        state->dev + GSR_PINNED_HEAVY_SEEN, heavy_expected, R,
                                         dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dfeatures, dL_dmeans3D, dL_dcov3D,
                                         dL_dsh, dL_dscales, dL_drotations, stream),
               "per-Gaussian backward");
@@ -641,17 +628,14 @@ extern "C" int gsr_filter(int P, int W, int H, const float* means3D, const float
     if (P < 0 || W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "bad sizes P=%d W=%d H=%d", P, W, H);
     if (P == 0) return GSR_OK;
     if (!means3D || !viewmatrix || !projmatrix || !radii) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "a required pointer is NULL");
-    {
-        const int rc0 = gsr_prefiltered_trap(P, prefiltered, debug, means3D, viewmatrix, stream);
-        if (rc0) return rc0;
-    }
+    const int rc = gsr_prefiltered_trap(P, prefiltered, debug, means3D, viewmatrix, stream);
+    if (rc) return rc;
     if ((!scales || !rotations) == (cov3D_precomp == nullptr))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "provide exactly one of scales+rotations or cov3D_precomp");
     if ((px == nullptr) != (py == nullptr)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "px and py go together");
-    GsrCam cam;
-    int rc = gsr_make_cam(cam, W, H, viewmatrix, projmatrix, nullptr, tan_fovx, tan_fovy, scale_modifier, stream);
-    if (rc) return rc;
-    GSR_STAGE(GSR_STAGE_PREPROCESS, gsr_launch_preprocess(px ? 2 : 1, P, 0, 0, cam, means3D, scales, rotations, nullptr, nullptr, nullptr,
+    const GsrCam cam = gsr_make_cam(W, H, viewmatrix, projmatrix, nullptr, tan_fovx, tan_fovy, scale_modifier);
+    GSR_STAGE(GSR_STAGE_PREPROCESS, stream, debug,
+              gsr_launch_preprocess(px ? 2 : 1, P, 0, 0, cam, means3D, scales, rotations, nullptr, nullptr, nullptr,
                                     cov3D_precomp, nullptr, nullptr, radii, px, py, 0, nullptr, stream),
               "filter preprocess");
     return GSR_OK;

@@ -1023,9 +1023,13 @@ static hipError_t gsr_allow_big_lds()
     return e;
 }
 
-hipError_t gsr_launch_count(int P, int T, int gx, const GsrGeom& geom, const GsrImage& image, uint32_t* info_host_mapped,
-                            bool defer_tile_scan, bool occlusion_cut, const uint32_t* walk_depths, bool* ordered, hipStream_t stream)
+hipError_t gsr_launch_count(const GsrFrame& f, uint32_t* info_host_mapped, bool defer_tile_scan, bool occlusion_cut,
+                            const uint32_t* walk_depths, bool* ordered)
 {
+    const int P = f.P, T = f.T, gx = f.gx;
+    const GsrGeom& geom = f.geom;
+    const GsrImage& image = f.image;
+    hipStream_t stream = f.stream;
     const int nchunks = gsr_num_chunks(P);
     if (ordered) *ordered = false;
     hipError_t e;
@@ -1092,18 +1096,21 @@ int gsr_scatter_bands(int P, int T, int gx, int expected_instances, int forced)
     return 1;  // nothing fits (huge image): the plain form with its direct stores
 }
 
-hipError_t gsr_launch_scatter(int P, int T, int gx, const GsrGeom& geom, const GsrImage& image, const GsrBinning& bin,
-                              int capacity, int expected_instances, int forced_bands, bool fused_tile_scan, uint32_t* fused_info_host, bool inference,
-                              bool occlusion_cut, hipStream_t stream)
+hipError_t gsr_launch_scatter(const GsrFrame& f, const GsrScatterPass& pass)
 {
+    const int P = f.P, T = f.T, gx = f.gx, capacity = f.capacity, expected_instances = pass.expected_instances;
+    const GsrGeom& geom = f.geom;
+    const GsrImage& image = f.image;
+    const GsrBinning& bin = f.bin;
+    hipStream_t stream = f.stream;
     const int nchunks = gsr_num_chunks(P);
-    uint32_t* const offsets = inference ? nullptr : geom.offsets;  // gradient-slot numbering: only a backward reads it
+    uint32_t* const offsets = pass.inference ? nullptr : geom.offsets;  // gradient-slot numbering: only a backward reads it
     const int gy = gx > 0 ? T / gx : 0;
-    const int nbands = gsr_scatter_bands(P, T, gx, expected_instances, forced_bands);
+    const int nbands = gsr_scatter_bands(P, T, gx, expected_instances, pass.forced_bands);
     GsrFusedScan fs = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    if (fused_tile_scan && T <= GSR_MAX_TILES_LDS)
-        fs = GsrFusedScan{ image.tile_count, image.ranges, image.info, image.tile_work, image.sorted_len, image.need_full, fused_info_host,
-                           occlusion_cut ? (const uint32_t*)image.occ_drop : (const uint32_t*)nullptr, image.tile_group };
+    if (pass.fused_tile_scan && T <= GSR_MAX_TILES_LDS)
+        fs = GsrFusedScan{ image.tile_count, image.ranges, image.info, image.tile_work, image.sorted_len, image.need_full, pass.fused_info_host,
+                           pass.occlusion_cut ? (const uint32_t*)image.occ_drop : (const uint32_t*)nullptr, image.tile_group };
     if (T > GSR_MAX_TILES_LDS) {
         hipLaunchKernelGGL(gsr_cursor_init_kernel, dim3((T + 255) / 256), dim3(256), 0, stream, T, image.ranges, image.table);
         hipLaunchKernelGGL((gsr_scatter_kernel<true, false>), dim3(nchunks), dim3(GSR_HIST_THREADS), 0, stream, P, T, gx, nchunks,
@@ -1175,12 +1182,13 @@ static hipError_t gsr_launch_full_sorts(int T, int capacity, uint32_t lo0, uint3
     return hipGetLastError();
 }
 
-hipError_t gsr_launch_tile_sort(int T, int capacity, int max_tile_count, int partial /* 0 = complete sorts, 1 = long lists bet on a sorted
-                                prefix, 2 = complete sorts, lists beyond GSR_NEAR_CAP in a launch of their own */, bool speculative, bool inference, const GsrGeom& geom,
-                                const GsrImage& image, const GsrBinning& bin_in, hipStream_t stream)
+hipError_t gsr_launch_tile_sort(const GsrFrame& f, int max_tile_count, int partial /* 0 = complete sorts, 1 = long lists bet on a sorted
+                                prefix, 2 = complete sorts, lists beyond GSR_NEAR_CAP in a launch of their own */, bool speculative, bool inference)
 {
-    (void)geom;
-    GsrBinning bin = bin_in;
+    const int T = f.T, capacity = f.capacity;
+    const GsrImage& image = f.image;
+    hipStream_t stream = f.stream;
+    GsrBinning bin = f.bin;
     if (inference) bin.slot_written = nullptr;
     // max_tile_count < 0: not known -> run every variant, blocks exit on mismatch.  speculative: max_tile_count is the
     // caller's guess (it sizes the LDS; the host checks it against the truth afterwards)
@@ -1206,10 +1214,9 @@ hipError_t gsr_launch_tile_sort(int T, int capacity, int max_tile_count, int par
 }
 
 // After a forward over partially sorted lists: full sort of the tiles that ran off their sorted prefix (need_full).
-hipError_t gsr_launch_sort_fixup(int T, int capacity, int max_tile_count, const GsrImage& image, const GsrBinning& bin,
-                                 bool inference, hipStream_t stream)
+hipError_t gsr_launch_sort_fixup(const GsrFrame& f, int max_tile_count, bool inference)
 {
-    if (capacity <= 0 || max_tile_count <= GSR_NEAR_CAP) return hipSuccess;
-    return gsr_launch_full_sorts(T, capacity, (uint32_t)GSR_NEAR_CAP, (uint32_t)max_tile_count, image, bin, image.need_full,
-                                 image.sorted_len, inference, stream);
+    if (f.capacity <= 0 || max_tile_count <= GSR_NEAR_CAP) return hipSuccess;
+    return gsr_launch_full_sorts(f.T, f.capacity, (uint32_t)GSR_NEAR_CAP, (uint32_t)max_tile_count, f.image, f.bin, f.image.need_full,
+                                 f.image.sorted_len, inference, f.stream);
 }

@@ -1157,18 +1157,22 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(GSR_BW
 }
 
 // ---------------------------------------------------------------------------------------------
-hipError_t gsr_launch_blend_forward(int W, int H, int gx, int T, const float* bg, const GsrGeom& geom,
-                                    const GsrImage& image, const GsrBinning& bin, float* out_color, float* out_depth,
-                                    float* out_feature, int capacity, int max_tile_count, bool only_flagged, bool inference,
-                                    uint32_t* walk_depths, bool walk_depths_valid, bool already_ordered, uint32_t* ranoff_report, uint32_t serial,
-                                    hipStream_t stream)
+hipError_t gsr_launch_blend_forward(const GsrFrame& f, const float* bg, float* out_color, float* out_depth, float* out_feature,
+                                    int max_tile_count, const GsrBlendPass& pass)
 {
+    const int W = f.W, H = f.H, gx = f.gx, T = f.T, capacity = f.capacity;
+    const GsrGeom& geom = f.geom;
+    const GsrImage& image = f.image;
+    const GsrBinning& bin = f.bin;
+    hipStream_t stream = f.stream;
+    const bool only_flagged = pass.only_flagged;
+    uint32_t* const walk_depths = pass.walk_depths;
     if (T <= 0) return hipSuccess;
     // per-view walk depths: order the tasks by the previous visit's (not in the fix-up pass: a few flagged tiles), record this visit's
     const int xt = gsr_xcd_tiles(T);
     const uint32_t* qorder = nullptr;
-    if (walk_depths && walk_depths_valid && !only_flagged && 4 * xt <= GSR_ORDER_MAX_SLOTS) {
-        if (!already_ordered)  // (the one-call forward had the column scan's launch do it)
+    if (walk_depths && pass.walk_depths_valid && !only_flagged && 4 * xt <= GSR_ORDER_MAX_SLOTS) {
+        if (!pass.already_ordered)  // (the one-call forward had the column scan's launch do it)
             hipLaunchKernelGGL(gsr_fwd_order_kernel, dim3(8), dim3(1024), 0, stream, T, xt, walk_depths, image.qorder);
         qorder = image.qorder;
     }
@@ -1177,18 +1181,22 @@ hipError_t gsr_launch_blend_forward(int W, int H, int gx, int T, const float* bg
                        gx, T, bg, out_color, out_depth, out_feature, image.final_T, image.n_contrib, image.tile_work, image.ckpt,     \
                        gsr_seg_len(T), (uint32_t)capacity, max_tile_count < 0 ? 0x7fffffffu : (uint32_t)max_tile_count,               \
                        image.sorted_len, image.need_full, only_flagged ? image.need_full : (const uint32_t*)nullptr, image.qresume, image.info + 3,        \
-                       qorder, walk_depths, only_flagged ? ranoff_report : (uint32_t*)nullptr, serial)
-    if (inference) GSR_FWD_LAUNCH(false);
+                       qorder, walk_depths, only_flagged ? pass.ranoff_report : (uint32_t*)nullptr, pass.serial)
+    if (pass.inference) GSR_FWD_LAUNCH(false);
     else GSR_FWD_LAUNCH(true);
 #undef GSR_FWD_LAUNCH
     return hipGetLastError();
 }
 
-hipError_t gsr_launch_blend_backward(int W, int H, int gx, int T, const float* bg, const GsrGeom& geom,
-                                     const GsrImage& image, const GsrBinning& bin, const float* dL_dcolor,
-                                     const float* dL_ddepth, const float* dL_dfeature, float* slots, uint8_t* slot_written,
-                                     uint32_t* heavy_groups, int max_tile_count, hipStream_t stream)
+hipError_t gsr_launch_blend_backward(const GsrFrame& f, const float* bg, const float* dL_dcolor, const float* dL_ddepth,
+                                     const float* dL_dfeature, float* slots, uint8_t* slot_written, uint32_t* heavy_groups,
+                                     int max_tile_count)
 {
+    const int W = f.W, H = f.H, gx = f.gx, T = f.T;
+    const GsrGeom& geom = f.geom;
+    const GsrImage& image = f.image;
+    const GsrBinning& bin = f.bin;
+    hipStream_t stream = f.stream;
     if (T <= 0) return hipSuccess;
     float4* s4 = reinterpret_cast<float4*>(slots);
     // the grid covers `nseg` segments of every tile -- as many as the frame's longest list has (round 6; rounds 4-5: all of them as soon

@@ -242,6 +242,10 @@ static inline int gsr_num_chunks(int P)
     return nb;
 }
 
+// the 16x16-pixel tile grid of a W x H image: the one place that rounds up
+struct GsrGrid { int gx, gy; };
+static inline GsrGrid gsr_tile_grid(int W, int H) { return { (W + GSR_TILE - 1) / GSR_TILE, (H + GSR_TILE - 1) / GSR_TILE }; }
+
 static inline GsrGeom gsr_carve_geom(void* base, int P)
 {
     GsrGeom g;
@@ -265,7 +269,8 @@ static inline GsrImage gsr_carve_image(void* base, int P, int W, int H)
     GsrImage im;
     size_t off = 0;
     char* b = (char*)base;
-    size_t gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
+    const GsrGrid grid = gsr_tile_grid(W, H);
+    size_t gx = grid.gx, gy = grid.gy;
     size_t T = gx * gy > 0 ? gx * gy : 1, N = (size_t)W * H > 0 ? (size_t)W * H : 1;
     im.ranges = (uint2*)(b + off); off += gsr_align(T * sizeof(uint2));
     im.final_T = (float*)(b + off); off += gsr_align(N * 4);
@@ -331,26 +336,50 @@ hipError_t gsr_launch_preprocess(int mode, int P, int D, int M, const GsrCam& ca
 hipError_t gsr_launch_prefiltered_check(int P, const float* means3D, const float* viewmatrix, uint32_t* culled, hipStream_t stream);
 hipError_t gsr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,
                                    hipStream_t stream);
-hipError_t gsr_launch_count(int P, int T, int gx, const GsrGeom& geom, const GsrImage& image, uint32_t* info_host_mapped,
-                            bool defer_tile_scan, bool occlusion_cut, const uint32_t* walk_depths /* order the forward's tasks by them, or NULL */,
-                            bool* ordered /* out: image.qorder was written by this launch */, hipStream_t stream);
+// One frame of one entry point: sizes, tile grid, the carved workspaces, stream and debug flag (api.hip builds it once; the launchers
+// below read what they need from it).  `bin` / `capacity`: the binning workspace and the instances it holds (unset before stage 2).
+struct GsrFrame {
+    int P, W, H, gx, gy, T;
+    GsrGeom geom;
+    GsrImage image;
+    GsrBinning bin;
+    int capacity;
+    hipStream_t stream;
+    int debug;  // synchronise and check after every stage (api.hip, GSR_STAGE)
+};
+// what one scatter launch is asked for
+struct GsrScatterPass {
+    int expected_instances;     // sizes the staging and the bands (gsr_scatter_bands): R, or what a speculative forward expects it to be
+    int forced_bands;           // gsr_tuning.scatter_bands (0 = choose)
+    bool fused_tile_scan;       // run the tile scan (ranges, R, longest list) inside the scatter kernel ...
+    uint32_t* fused_info_host;  // ... which then stores {R, longest list} into this host-mapped word pair
+    bool inference;             // no backward will follow: no gradient-slot numbering
+    bool occlusion_cut;
+};
+// what one forward-blend launch is asked for
+struct GsrBlendPass {
+    bool only_flagged;        // fix-up pass: only the tiles that ran off their sorted prefix (image.need_full)
+    bool inference;
+    uint32_t* walk_depths;    // gsr_tuning.walk_depths (or NULL): this visit's walk depths are recorded here ...
+    bool walk_depths_valid;   // ... and it already holds a previous visit's: dispatch the deepest walks first
+    bool already_ordered;     // image.qorder was written by the column scan's launch (gsr_launch_count)
+    uint32_t* ranoff_report;  // fix-up pass: host-mapped word a resumed quadrant stores `serial` into
+    uint32_t serial;
+};
+
+hipError_t gsr_launch_count(const GsrFrame& f, uint32_t* info_host_mapped, bool defer_tile_scan, bool occlusion_cut,
+                            const uint32_t* walk_depths /* order the forward's tasks by them, or NULL */,
+                            bool* ordered /* out: image.qorder was written by this launch */);
 int gsr_scatter_bands(int P, int T, int gx, int expected_instances, int forced);  // bands of tile rows per chunk in the scatter launch (binning.hip)
-hipError_t gsr_launch_scatter(int P, int T, int gx, const GsrGeom& geom, const GsrImage& image, const GsrBinning& bin,
-                              int capacity, int expected_instances, int forced_bands, bool fused_tile_scan, uint32_t* fused_info_host, bool inference,
-                              bool occlusion_cut, hipStream_t stream);
-hipError_t gsr_launch_tile_sort(int T, int capacity, int max_tile_count, int partial /* 0 complete, 1 prefix bet, 2 complete with the long lists apart */, bool speculative, bool inference, const GsrGeom& geom, const GsrImage& image,
-                                const GsrBinning& bin, hipStream_t stream);
-hipError_t gsr_launch_blend_forward(int W, int H, int gx, int T, const float* bg, const GsrGeom& geom,
-                                    const GsrImage& image, const GsrBinning& bin, float* out_color, float* out_depth,
-                                    float* out_feature, int capacity, int max_tile_count, bool only_flagged, bool inference,
-                                    uint32_t* walk_depths, bool walk_depths_valid, bool already_ordered, uint32_t* ranoff_report /* fix-up pass: host-mapped word */,
-                                    uint32_t serial, hipStream_t stream);
-hipError_t gsr_launch_sort_fixup(int T, int capacity, int max_tile_count, const GsrImage& image, const GsrBinning& bin,
-                                 bool inference, hipStream_t stream);
-hipError_t gsr_launch_blend_backward(int W, int H, int gx, int T, const float* bg, const GsrGeom& geom,
-                                     const GsrImage& image, const GsrBinning& bin, const float* dL_dcolor,
-                                     const float* dL_ddepth, const float* dL_dfeature, float* slots,
-                                     uint8_t* slot_written, uint32_t* heavy_groups, int max_tile_count /* < 0: unknown */, hipStream_t stream);
+hipError_t gsr_launch_scatter(const GsrFrame& f, const GsrScatterPass& pass);
+hipError_t gsr_launch_tile_sort(const GsrFrame& f, int max_tile_count, int partial /* 0 complete, 1 prefix bet, 2 complete with the long lists apart */,
+                                bool speculative, bool inference);
+hipError_t gsr_launch_blend_forward(const GsrFrame& f, const float* bg, float* out_color, float* out_depth, float* out_feature,
+                                    int max_tile_count, const GsrBlendPass& pass);
+hipError_t gsr_launch_sort_fixup(const GsrFrame& f, int max_tile_count, bool inference);
+hipError_t gsr_launch_blend_backward(const GsrFrame& f, const float* bg, const float* dL_dcolor, const float* dL_ddepth,
+                                     const float* dL_dfeature, float* slots, uint8_t* slot_written, uint32_t* heavy_groups,
+                                     int max_tile_count /* < 0: unknown */);
 hipError_t gsr_launch_gauss_backward(int P, int D, int M, const GsrCam& cam, const float* means3D, const int32_t* radii,
                                      const float* shs, const float* scales, const float* rotations,
                                      const float* cov3D_precomp, const GsrGeom& geom, const float* slots,

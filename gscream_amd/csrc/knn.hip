@@ -327,13 +327,14 @@ hipError_t gsk_launch(int P, const float* points, float* mean_dist2, void* works
     hipLaunchKernelGGL(gsk_bucket_scatter_kernel, dim3(nb256), dim3(256), 0, stream, P, w.codes, w.cursor, w.seg_keys);
     {   // every bucket's segment in key order, by the rasterizer's per-segment sort (longest segment unknown on the host: all
         // size classes are launched, workgroups of the wrong class leave at once); ids_sorted = the keys' low words in order
-        GsrGeom geom{};
-        GsrImage image{};
-        GsrBinning bin{};
-        image.ranges = w.ranges;
-        bin.seg_keys = w.seg_keys;
-        bin.point_list = w.ids_sorted;
-        e = gsr_launch_tile_sort(GSK_BUCKETS, P, -1, false, false, true, geom, image, bin, stream);
+        GsrFrame f{};
+        f.T = GSK_BUCKETS;
+        f.capacity = P;
+        f.image.ranges = w.ranges;
+        f.bin.seg_keys = w.seg_keys;
+        f.bin.point_list = w.ids_sorted;
+        f.stream = stream;
+        e = gsr_launch_tile_sort(f, -1, 0 /* complete sorts */, false, true /* no written-slot flags */);
         if (e != hipSuccess) { *why = "bucket sort"; return e; }
     }
     const int nboxes = (P + GSK_BOX - 1) / GSK_BOX;

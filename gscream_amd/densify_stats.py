@@ -6,7 +6,6 @@ accumulates, in place, `model.opacity_accum[N,1]`, `model.anchor_demon[N,1]`, `m
 and `model.offset_denom[N*K,1]` from one rendered view -- one kernel (gsr_training_stats) instead of ~15 boolean-mask
 indexing ops.  Arguments as in the reference: `opacity` = the decode's neural_opacity [Nv*K,1], `offset_selection_mask`
 its mask [Nv*K], `update_filter` = radii > 0 over the decoded Gaussians [M], `viewspace_point_tensor.grad` [M,3]."""
-import ctypes
 
 import torch
 
@@ -16,7 +15,6 @@ __all__ = ["training_statis"]
 
 
 def training_statis(model, viewspace_point_tensor, opacity, update_filter, offset_selection_mask, anchor_visible_mask):
-    lib = _native.load()
     K = int(model.n_offsets)
     acc = model.opacity_accum
     if not acc.is_cuda:
@@ -52,9 +50,6 @@ def training_statis(model, viewspace_point_tensor, opacity, update_filter, offse
     # another render than update_filter; same here (the kernel additionally never reads beyond row M)
     if kept != M:
         raise ValueError(f"offset_selection_mask keeps {kept} offsets but update_filter has {M} entries (masks of different renders?)")
-    with torch.cuda.device(dev):
-        _native.check(lib.gsr_training_stats(Nv, K, M, _native.ptr(vis), _native.ptr(nop), _native.ptr(sel), _native.ptr(first),
-                                             _native.ptr(uf), _native.ptr(grad), _native.ptr(model.opacity_accum),
-                                             _native.ptr(model.anchor_demon), _native.ptr(model.offset_gradient_accum),
-                                             _native.ptr(model.offset_denom),
-                                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_training_stats")
+    _native.run("gsr_training_stats", dev, Nv, K, M, _native.ptr(vis), _native.ptr(nop), _native.ptr(sel), _native.ptr(first),
+                _native.ptr(uf), _native.ptr(grad), _native.ptr(model.opacity_accum), _native.ptr(model.anchor_demon),
+                _native.ptr(model.offset_gradient_accum), _native.ptr(model.offset_denom))

@@ -17,7 +17,6 @@ image argument only (the ground truth is a constant in the trainer).  There is n
 a HIP device.  `window_size`: odd, up to 11 (11 everywhere in GScream).  Differences from the reference: the window is applied separably (two 11-tap passes) instead of
 as one 121-tap depthwise conv2d, so values agree to fp32 rounding (~1e-6), not bit for bit.
 """
-import ctypes
 
 import torch
 
@@ -47,10 +46,6 @@ def _prep(img, gt, weight):
     return x, y, w, C, H, W
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class _FusedLoss(torch.autograd.Function):
     """L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m)."""
 
@@ -59,12 +54,10 @@ class _FusedLoss(torch.autograd.Function):
         lib = _native.load()
         x, y, w, C, H, W = _prep(img, gt, weight)
         need_grad = img.requires_grad
-        with torch.cuda.device(x.device):
-            ws = torch.empty((lib.gsr_loss_workspace_bytes(C, H, W),), dtype=torch.uint8, device=x.device)
-            out = torch.empty((3,), dtype=torch.float32, device=x.device)
-            _native.check(lib.gsr_rgb_loss_forward_window(C, H, W, _native.ptr(x), _native.ptr(y), _native.ptr(w), float(a_l1),
-                                                          float(a_ssim), int(window_size), _native.ptr(ws), _native.ptr(out),
-                                                          int(need_grad), _stream()), "gsr_rgb_loss_forward")
+        ws = torch.empty((lib.gsr_loss_workspace_bytes(C, H, W),), dtype=torch.uint8, device=x.device)
+        out = torch.empty((3,), dtype=torch.float32, device=x.device)
+        _native.run("gsr_rgb_loss_forward_window", x.device, C, H, W, _native.ptr(x), _native.ptr(y), _native.ptr(w), float(a_l1),
+                    float(a_ssim), int(window_size), _native.ptr(ws), _native.ptr(out), int(need_grad))
         ctx.save_for_backward(x, y, w if w is not None else torch.empty(0, device=x.device), ws)
         ctx.coef = (float(a_l1), float(a_ssim))
         ctx.window_size = int(window_size)
@@ -74,15 +67,12 @@ class _FusedLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
-        lib = _native.load()
         x, y, w, ws = ctx.saved_tensors
         C, H, W = x.shape
         up = g_loss.detach().reshape(1).float().contiguous()
-        with torch.cuda.device(x.device):
-            grad = torch.empty_like(x)
-            _native.check(lib.gsr_rgb_loss_backward_window(C, H, W, _native.ptr(x), _native.ptr(y), _native.ptr(w), ctx.coef[0],
-                                                           ctx.coef[1], ctx.window_size, _native.ptr(ws), _native.ptr(up),
-                                                           _native.ptr(grad), _stream()), "gsr_rgb_loss_backward")
+        grad = torch.empty_like(x)
+        _native.run("gsr_rgb_loss_backward_window", x.device, C, H, W, _native.ptr(x), _native.ptr(y), _native.ptr(w), ctx.coef[0],
+                    ctx.coef[1], ctx.window_size, _native.ptr(ws), _native.ptr(up), _native.ptr(grad))
         return grad.reshape(ctx.in_shape), None, None, None, None, None
 
 
@@ -137,12 +127,10 @@ class _DepthLoss(torch.autograd.Function):
             raise ValueError("depth and target must be [1,H,W] / [H,W] maps of the same size")
         f = lambda t: None if t is None else t.detach().reshape(H, W).contiguous().float()
         d, y, m, w, g = f(depth), f(target), f(lsq_mask), f(l1_weight), f(grad_mask)
-        with torch.cuda.device(d.device):
-            ws = torch.empty((lib.gsr_depth_loss_workspace_bytes(H, W),), dtype=torch.uint8, device=d.device)
-            out = torch.empty((5,), dtype=torch.float32, device=d.device)
-            _native.check(lib.gsr_depth_loss_forward(H, W, _native.ptr(d), _native.ptr(y), _native.ptr(m), _native.ptr(w),
-                                                     _native.ptr(g), float(lambda_l1), float(lambda_smooth), _native.ptr(ws),
-                                                     _native.ptr(out), _stream()), "gsr_depth_loss_forward")
+        ws = torch.empty((lib.gsr_depth_loss_workspace_bytes(H, W),), dtype=torch.uint8, device=d.device)
+        out = torch.empty((5,), dtype=torch.float32, device=d.device)
+        _native.run("gsr_depth_loss_forward", d.device, H, W, _native.ptr(d), _native.ptr(y), _native.ptr(m), _native.ptr(w),
+                    _native.ptr(g), float(lambda_l1), float(lambda_smooth), _native.ptr(ws), _native.ptr(out))
         ctx.save_for_backward(d, y, m if m is not None else torch.empty(0, device=d.device), ws)
         ctx.in_shape = tuple(depth.shape)
         ctx.mark_non_differentiable(out)
@@ -150,14 +138,12 @@ class _DepthLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
-        lib = _native.load()
         d, y, m, ws = ctx.saved_tensors
         H, W = d.shape
         up = g_loss.detach().reshape(1).float().contiguous()
-        with torch.cuda.device(d.device):
-            grad = torch.empty_like(d)
-            _native.check(lib.gsr_depth_loss_backward(H, W, _native.ptr(d), _native.ptr(y), _native.ptr(m), _native.ptr(ws),
-                                                      _native.ptr(up), _native.ptr(grad), _stream()), "gsr_depth_loss_backward")
+        grad = torch.empty_like(d)
+        _native.run("gsr_depth_loss_backward", d.device, H, W, _native.ptr(d), _native.ptr(y), _native.ptr(m), _native.ptr(ws),
+                    _native.ptr(up), _native.ptr(grad))
         return grad.reshape(ctx.in_shape), None, None, None, None, None, None
 
 

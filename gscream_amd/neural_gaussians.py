@@ -22,10 +22,6 @@ from . import _native
 __all__ = ["generate_neural_gaussians", "decode"]
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _weight_array(ws):
     arr = (ctypes.c_void_p * 16)(*[w.data_ptr() for w in ws])
     return arr
@@ -37,7 +33,6 @@ class _Decode(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, anchor, offsets, gscale, campos, vis_idx, vis_mask, *weights):
-        lib = _native.load()
         if not feat.is_cuda:
             raise RuntimeError("gscream_amd.neural_gaussians: tensors must be on a HIP device (no CPU fallback)")
         K = int(offsets.shape[1])
@@ -59,7 +54,7 @@ class _Decode(torch.autograd.Function):
         feat_c, anchor_c, off_c, gs_c, cam_c = f32(feat), f32(anchor), f32(offsets), f32(gscale), f32(campos)
         ws = [f32(w) for w in weights]
         warr = _weight_array(ws)
-        with torch.cuda.device(dev):
+        with _native.on_device(dev.index):  # (the event below is recorded on the current device's stream)
             nop = torch.empty((N * K, 1), dtype=torch.float32, device=dev)
             mask = torch.empty((N * K,), dtype=torch.uint8, device=dev)
             count = torch.empty((max(N, 1),), dtype=torch.uint8, device=dev)
@@ -71,11 +66,10 @@ class _Decode(torch.autograd.Function):
                 vmask8 = vis_mask.detach().contiguous().view(torch.uint8)
                 vis = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
                 vis_count = total[1:]
-                _native.check(lib.gsr_decode_visible_rows(N, _native.ptr(vmask8), _native.ptr(vis), _native.ptr(vis_count), _native.ptr(scratch),
-                                                          _stream()), "gsr_decode_visible_rows")
-            _native.check(lib.gsr_decode_count(N, K, warr, _native.ptr(vis), _native.ptr(vis_count), _native.ptr(feat_c), _native.ptr(anchor_c), _native.ptr(cam_c),
-                                               _native.ptr(nop), _native.ptr(mask), _native.ptr(count), _native.ptr(first),
-                                               _native.ptr(total), _native.ptr(scratch), _stream()), "gsr_decode_count")
+                _native.run("gsr_decode_visible_rows", dev, N, _native.ptr(vmask8), _native.ptr(vis), _native.ptr(vis_count), _native.ptr(scratch))
+            _native.run("gsr_decode_count", dev, N, K, warr, _native.ptr(vis), _native.ptr(vis_count), _native.ptr(feat_c), _native.ptr(anchor_c),
+                        _native.ptr(cam_c), _native.ptr(nop), _native.ptr(mask), _native.ptr(count), _native.ptr(first),
+                        _native.ptr(total), _native.ptr(scratch))
             # The row count M has to reach the host (the outputs' shapes), as it does in the reference's boolean-mask indexing --
             # but the GPU need not wait for that round trip: the emit pass only needs the per-anchor first rows, which are on
             # the device, so it is enqueued BEFORE the read against buffers provisioned for every offset (N*K rows, 60 B each),
@@ -87,10 +81,9 @@ class _Decode(torch.autograd.Function):
             cap = N * K
             e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
             xyz, color, opacity, unc, scaling, rot = e(cap, 3), e(cap, 3), e(cap, 1), e(cap, 1), e(cap, 3), e(cap, 4)
-            _native.check(lib.gsr_decode_emit(N, K, warr, _native.ptr(vis), _native.ptr(vis_count), _native.ptr(feat_c), _native.ptr(anchor_c), _native.ptr(off_c),
-                                              _native.ptr(gs_c), _native.ptr(cam_c), _native.ptr(nop), _native.ptr(mask), _native.ptr(first),
-                                              _native.ptr(xyz), _native.ptr(color), _native.ptr(opacity), _native.ptr(unc),
-                                              _native.ptr(scaling), _native.ptr(rot), _stream()), "gsr_decode_emit")
+            _native.run("gsr_decode_emit", dev, N, K, warr, _native.ptr(vis), _native.ptr(vis_count), _native.ptr(feat_c), _native.ptr(anchor_c),
+                        _native.ptr(off_c), _native.ptr(gs_c), _native.ptr(cam_c), _native.ptr(nop), _native.ptr(mask), _native.ptr(first),
+                        _native.ptr(xyz), _native.ptr(color), _native.ptr(opacity), _native.ptr(unc), _native.ptr(scaling), _native.ptr(rot))
             ev.synchronize()   # waits for the count pass only: the copy was enqueued in front of the emit pass
             M = int(pin[0])
             xyz, color, opacity, unc, scaling, rot = xyz[:M], color[:M], opacity[:M], unc[:M], scaling[:M], rot[:M]
@@ -123,7 +116,7 @@ class _Decode(torch.autograd.Function):
         z = lambda g, c: (None if g is None else g.detach().contiguous().float())  # noqa: E731
         g_xyz, g_color, g_opacity, g_unc, g_scaling, g_rot = z(g_xyz, 3), z(g_color, 3), z(g_opacity, 1), z(g_unc, 1), z(g_scaling, 3), z(g_rot, 4)
         warr = _weight_array(ws)
-        with torch.cuda.device(dev):
+        with _native.on_device(dev.index):
             e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
             vis = ctx.vis
             full = feat_c.shape[0]  # model-sized gradients; rows outside `vis` stay zero
@@ -148,14 +141,14 @@ class _Decode(torch.autograd.Function):
             gw1, gb1, gw2, gb2 = views[0:4], views[4:8], views[8:12], views[12:16]
             garr = (ctypes.c_void_p * 16)(*[g.data_ptr() for g in gw1 + gb1 + gw2 + gb2])
             wsp = _workspace(dev, lib.gsr_decode_weight_grad_workspace_bytes())
-            _native.check(lib.gsr_decode_backward(
-                N, K, warr, _native.ptr(vis), _native.ptr(feat_c), _native.ptr(anchor_c), _native.ptr(off_c), _native.ptr(gs_c),
+            _native.run(
+                "gsr_decode_backward", dev, N, K, warr, _native.ptr(vis), _native.ptr(feat_c), _native.ptr(anchor_c), _native.ptr(off_c), _native.ptr(gs_c),
                 _native.ptr(cam_c), _native.ptr(mask), _native.ptr(first), _native.ptr(g_xyz), _native.ptr(g_color), _native.ptr(g_opacity),
                 _native.ptr(g_unc), _native.ptr(g_scaling), _native.ptr(g_rot), _native.ptr(d_feat), _native.ptr(d_anchor),
-                _native.ptr(d_off), _native.ptr(d_gs), _native.ptr(wsp), garr, _stream()), "gsr_decode_backward")
+                _native.ptr(d_off), _native.ptr(d_gs), _native.ptr(wsp), garr)
             if hidden_by_kernel:
-                _native.check(lib.gsr_decode_zero_hidden_rows(full, K, _native.ptr(vis_mask8), _native.ptr(d_feat), _native.ptr(d_anchor),
-                                                              _native.ptr(d_off), _native.ptr(d_gs), _stream()), "gsr_decode_zero_hidden_rows")
+                _native.run("gsr_decode_zero_hidden_rows", dev, full, K, _native.ptr(vis_mask8), _native.ptr(d_feat), _native.ptr(d_anchor),
+                            _native.ptr(d_off), _native.ptr(d_gs))
         grads_w = gw1 + gb1 + gw2 + gb2
         sh = ctx.in_shapes
         return (d_feat.reshape(sh[0]), d_anchor.reshape(sh[1]), d_off.reshape(sh[2]), d_gs.reshape(sh[3]), None, None, None,

@@ -131,7 +131,7 @@ def set_tuning(tile_cull=True, speculative=True, partial_sort=True, scatter_band
     _occlusion_mode[0] = occlusion_cut
     _occlusion_state.clear()
     lib = _native._lib  # (the library's own feedback heuristics start over too: the partial sort's bet, gsraster.h gsr_adaptive_reset)
-    if lib is not None and hasattr(lib, "gsr_adaptive_reset"):
+    if lib is not None:
         lib.gsr_adaptive_reset()
     _sync_tuning_variants()
     _capacity_hint.clear()
@@ -161,7 +161,6 @@ def _require_gpu(t, name):
 
 _F32 = torch.float32
 _EMPTY = torch.Tensor([])
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # the handle without building a torch.cuda.Stream
 
 
 def _f32c(t, device=None):
@@ -180,37 +179,6 @@ def _f32c(t, device=None):
 def _p(t):
     """device address for the C ABI: None (NULL) for absent / empty tensors (the reference's 'not provided')"""
     return t.data_ptr() if (t is not None and t.numel() != 0) else None
-
-
-def _stream_handle(index):
-    """HIP stream handle of torch's current stream on device `index` (what the kernels are enqueued on)."""
-    if _raw_stream is not None:
-        return _raw_stream(index)
-    return torch.cuda.current_stream(index).cuda_stream
-
-
-def _stream():
-    return _native.ctypes.c_void_p(_stream_handle(torch.cuda.current_device()))
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` that costs nothing when `dev` already is the current device (the training case)."""
-    __slots__ = ("index", "prev")
-
-    def __init__(self, index):
-        self.index, self.prev = index, -1
-
-    def __enter__(self):
-        cur = torch.cuda.current_device()
-        if cur != self.index:
-            self.prev = cur
-            torch.cuda.set_device(self.index)
-        return self.index
-
-    def __exit__(self, *exc):
-        if self.prev >= 0:
-            torch.cuda.set_device(self.prev)
-        return False
 
 
 def _snapshot(args):
@@ -276,8 +244,8 @@ def _forward_native(means3D, sh, colors_precomp, opacities, uncertainties, scale
               float(rs.tanfovx), float(rs.tanfovy), 1 if rs.prefiltered else 0)
     gp, ip, bgp = geom.data_ptr(), img.data_ptr(), _p(bg)
     cp, dp, up, rp = color.data_ptr(), depth.data_ptr(), unc.data_ptr(), radii.data_ptr()
-    with _on_device(idx):
-        stream = _stream_handle(idx)
+    with _native.on_device(idx):
+        stream = _native.stream_handle(idx)
         cap, tile_hint = _capacity_hint.get(idx, (0, 0))
         done = False
         if cap > 0 and not _tuning.disable_speculation:
@@ -369,7 +337,7 @@ def _backward_native(rs, num_rendered, binning_capacity, means3D, radii, colors_
     means3D_c, colors_c, sh_c = _f32c(means3D), _f32c(colors_precomp, dev), _f32c(sh, dev)
     scales_c, rot_c, cov_c = _f32c(scales, dev), _f32c(rotations, dev), _f32c(cov3Ds_precomp, dev)
     scratch = mk((lib.gsr_backward_scratch_bytes(P, num_rendered),), dtype=torch.uint8, device=dev)
-    with _on_device(idx):
+    with _native.on_device(idx):
         rc = lib.gsr_backward(
             P, int(rs.sh_degree), M, W, H, int(num_rendered), int(binning_capacity), int(max_tile_count), _p(bg), means3D_c.data_ptr(),
             radii.data_ptr(), _p(colors_c), _p(sh_c), _p(scales_c), float(rs.scale_modifier), _p(rot_c),
@@ -377,7 +345,7 @@ def _backward_native(rs, num_rendered, binning_capacity, means3D, radii, colors_
             _p(geom), _p(img), _p(binning), scratch.data_ptr(),
             g_means2D.data_ptr(), g_colors.data_ptr(), g_opac.data_ptr(), g_feat.data_ptr(),
             g_means3D.data_ptr(), _p(g_cov), _p(g_sh), _p(g_scales), _p(g_rot),
-            _tuning_ref, 1 if rs.debug else 0, _stream_handle(idx))
+            _tuning_ref, 1 if rs.debug else 0, _native.stream_handle(idx))
         if rc != 0:
             _native.check(rc, "gsr_backward")
     return g_means2D, g_colors, g_opac, g_feat, g_means3D, g_cov, g_sh, g_scales, g_rot
@@ -492,7 +460,6 @@ class GaussianRasterizer(nn.Module):
 
     def markVisible(self, positions):
         """bool[P]: view-space z > 0.2 (DGR/__init__.py:208-217, rasterizer_impl.cu:54-66)."""
-        lib = _native.load()
         rs = self.raster_settings
         with torch.no_grad():
             _require_gpu(positions, "positions")
@@ -502,10 +469,7 @@ class GaussianRasterizer(nn.Module):
             if P:
                 view, proj, _ = _cam(rs, dev)
                 pos_c = _f32c(positions)
-                with torch.cuda.device(dev):
-                    rc = lib.gsr_mark_visible(P, _native.ptr(pos_c), _native.ptr(view), _native.ptr(proj),
-                                              _native.ptr(present), _stream())
-                _native.check(rc, "gsr_mark_visible")
+                _native.run("gsr_mark_visible", dev, P, _native.ptr(pos_c), _native.ptr(view), _native.ptr(proj), _native.ptr(present))
         return present
 
     def forward(self, means3D, means2D, opacities, uncertainties, shs=None, colors_precomp=None, scales=None,
@@ -529,7 +493,6 @@ class GaussianRasterizer(nn.Module):
             raster_settings)
 
     def _filter(self, means3D, scales, rotations, cov3D_precomp, want_xy):
-        lib = _native.load()
         rs = self.raster_settings
         with torch.no_grad():
             if means3D.dim() != 2 or means3D.shape[1] != 3:
@@ -545,14 +508,12 @@ class GaussianRasterizer(nn.Module):
                 view, proj, _ = _cam(rs, dev)
                 means_c, scales_c = _f32c(means3D), _f32c(scales, dev)  # e.g. get_scaling[:, :3] is a strided slice
                 rot_c, cov_c = _f32c(rotations, dev), _f32c(cov3D_precomp, dev)
-                with torch.cuda.device(dev):
-                    rc = lib.gsr_filter(
-                        P, int(rs.image_width), int(rs.image_height), _native.ptr(means_c),
-                        _native.ptr(scales_c), float(rs.scale_modifier), _native.ptr(rot_c),
-                        _native.ptr(cov_c), _native.ptr(view), _native.ptr(proj),
-                        float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)), _native.ptr(radii),
-                        _native.ptr(px), _native.ptr(py), int(bool(rs.debug)), _stream())
-                _native.check(rc, "gsr_filter")
+                _native.run(
+                    "gsr_filter", dev, P, int(rs.image_width), int(rs.image_height), _native.ptr(means_c),
+                    _native.ptr(scales_c), float(rs.scale_modifier), _native.ptr(rot_c),
+                    _native.ptr(cov_c), _native.ptr(view), _native.ptr(proj),
+                    float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)), _native.ptr(radii),
+                    _native.ptr(px), _native.ptr(py), int(bool(rs.debug)))
         return radii, px, py
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):

@@ -11,7 +11,6 @@ reads only the values, scene/gaussian_model.py:874).
 fp32 `src` of one or two dimensions reduced along dim 0 with a row index (1-D, or 2-D broadcast from one column such as
 `index.unsqueeze(1).expand(-1, F)`) and no `out` runs one HIP kernel sequence (gsr_scatter_max).  Every other form runs exact
 torch (scatter_reduce "amax" + an argmax pass): a different dtype or layout, not a missing kernel."""
-import ctypes
 
 import torch
 
@@ -74,7 +73,6 @@ def scatter_max(src, index, dim=-1, out=None, dim_size=None):
     rows = _row_index(src, index, dim) if out is None else None
     if rows is None:
         return _torch_scatter_max(src, index, dim, out, int(dim_size))
-    lib = _native.load()
     src = src.detach().contiguous()
     rows = rows.detach().long().contiguous()
     R = int(src.shape[0])
@@ -83,7 +81,5 @@ def scatter_max(src, index, dim=-1, out=None, dim_size=None):
     shape = (S, F) if src.dim() == 2 else (S,)
     res = torch.empty(shape, dtype=torch.float32, device=src.device)
     arg = torch.empty(shape, dtype=torch.long, device=src.device)
-    with torch.cuda.device(src.device):
-        _native.check(lib.gsr_scatter_max(R, F, S, _native.ptr(src), _native.ptr(rows), _native.ptr(res), _native.ptr(arg),
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_scatter_max")
+    _native.run("gsr_scatter_max", src.device, R, F, S, _native.ptr(src), _native.ptr(rows), _native.ptr(res), _native.ptr(arg))
     return res, arg
