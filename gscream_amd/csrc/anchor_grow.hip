@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_scan.h"
 
 #define GAG_THREADS 256
 #define GAG_BIAS (1 << 20)
@@ -64,48 +65,11 @@ __device__ __forceinline__ uint32_t gag_hash(int x, int y, int z)
 __device__ __forceinline__ float gag_cell(float x, float inv) { return rintf(__fmul_rn(x, inv)); }
 __device__ __forceinline__ bool gag_in_range(float q) { return q >= -(float)GAG_BIAS && q < (float)GAG_BIAS; }
 
-// ---- scans: 64-bit inclusive wave scan, exclusive block scan of 256 threads --------------------------------------------
-__device__ __forceinline__ unsigned long long gag_wave_scan(unsigned long long v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long gag_block_scan(unsigned long long v, unsigned long long* total)
-{
-    __shared__ unsigned long long wsum[GAG_THREADS / 64];
-    const unsigned long long incl = gag_wave_scan(v);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wsum[wave] = incl;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < GAG_THREADS / 64; w++) { base += w < wave ? wsum[w] : 0ull; tot += wsum[w]; }
-    if (total) *total = tot;
-    return base + incl - v;
-}
-
-// exclusive scan of the block totals in place (one block of 1024; thread i owns a contiguous run); the grand total's low and high
-// 32-bit halves go to *lo / *hi when given
+// exclusive scan of the block totals in place; the grand total's low and high 32-bit halves go to *lo / *hi when given
 __global__ void __launch_bounds__(1024) gag_top_scan_kernel(int nb, unsigned long long* __restrict__ block_sum, int32_t* __restrict__ lo,
                                                             int32_t* __restrict__ hi)
 {
-    __shared__ unsigned long long wsum[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int per = (nb + 1023) / 1024, i0 = threadIdx.x * per;
-    unsigned long long s = 0;
-    for (int i = 0; i < per; i++) s += i0 + i < nb ? block_sum[i0 + i] : 0ull;
-    const unsigned long long incl = gag_wave_scan(s);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    unsigned long long run = incl - s, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const unsigned long long sw = wsum[w]; run += w < wave ? sw : 0ull; tot += sw; }
-    for (int i = 0; i < per && i0 + i < nb; i++) { const unsigned long long v = block_sum[i0 + i]; block_sum[i0 + i] = run; run += v; }
+    const unsigned long long tot = gsr_top_scan(nb, block_sum);
     if (threadIdx.x == 0) {
         if (lo) lo[0] = (int32_t)(uint32_t)tot;
         if (hi) hi[0] = (int32_t)(uint32_t)(tot >> 32);
@@ -163,7 +127,8 @@ __global__ void __launch_bounds__(GAG_THREADS) gag_mask_count_kernel(int L, cons
                                                                      unsigned long long* __restrict__ block_sum)
 {
     const int i = blockIdx.x * GAG_THREADS + threadIdx.x;
-    const int c = __syncthreads_count(i < L && mask[i] != 0);
+    uint32_t c;
+    (void)gsr_block_rank<GAG_THREADS>(i < L && mask[i] != 0, &c);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = (unsigned long long)c;
 }
 
@@ -176,7 +141,7 @@ __global__ void __launch_bounds__(GAG_THREADS) gag_place_kernel(int L, int K, co
 {
     const int i = blockIdx.x * GAG_THREADS + threadIdx.x;
     const bool set = i < L && mask[i] != 0;
-    const unsigned long long pos = block_base[blockIdx.x] + gag_block_scan(set ? 1ull : 0ull, nullptr);
+    const unsigned long long pos = block_base[blockIdx.x] + gsr_block_rank<GAG_THREADS>(set);
     if (!set) return;
     const int n = (int)((uint32_t)i / (uint32_t)K);
     float q[3];
@@ -221,7 +186,7 @@ __global__ void __launch_bounds__(GAG_THREADS) gag_head_count_kernel(int M, cons
     const unsigned long long v = gag_head_value(s, M, keys, cells, table, cap_mask);
     if (s < M) head_kind[s] = (uint8_t)((v & 1ull) | ((v >> 31) & 2ull));
     unsigned long long tot;
-    (void)gag_block_scan(v, &tot);
+    (void)gsr_block_scan_excl<GAG_THREADS>(v, &tot);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = tot;
 }
 
@@ -234,7 +199,7 @@ __global__ void __launch_bounds__(GAG_THREADS) gag_head_place_kernel(int M, cons
     const int s = blockIdx.x * GAG_THREADS + threadIdx.x;
     const uint8_t hk = s < M ? head_kind[s] : (uint8_t)0;
     const unsigned long long v = (unsigned long long)(hk & 1u) | ((unsigned long long)(hk >> 1) << 32);
-    const unsigned long long excl = block_base[blockIdx.x] + gag_block_scan(v, nullptr);
+    const unsigned long long excl = block_base[blockIdx.x] + gsr_block_scan_excl<GAG_THREADS>(v);
     if (s >= M) return;
     const unsigned long long incl = excl + v;
     const uint32_t seg = (uint32_t)incl - 1u;

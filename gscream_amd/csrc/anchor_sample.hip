@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_scan.h"
 
 #define GAS_THREADS 256
 #define GAS_ITEMS 8                          // anchors per thread in the histogram sweeps
@@ -148,23 +149,10 @@ __global__ void __launch_bounds__(GAS_THREADS) gas_hist_kernel(int N, int level,
     if (any) gas_flush(lh, head + GAS_HIST0 + level * 2 * GAS_BINS);
 }
 
-__device__ __forceinline__ uint32_t gas_wave_scan32(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
 // One block of 1024: thread t owns bins 2t and 2t + 1 of each class.  The digit d of a class is the first whose inclusive count
 // reaches `take`; the anchors below it are all taken, `take` becomes what is still to be taken inside d.
 __global__ void __launch_bounds__(1024) gas_pick_kernel(int level, int max_pairs, uint32_t* __restrict__ head, int32_t* __restrict__ info)
 {
-    __shared__ uint32_t wsum[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t take[2];
     if (level == 0) {
         const uint32_t n_fg = head[1], n_bg = head[2];
@@ -187,72 +175,36 @@ __global__ void __launch_bounds__(1024) gas_pick_kernel(int level, int max_pairs
     const int bins = gas_bins(level), shift = gas_shift(level);
     const uint32_t* hist = head + GAS_HIST0 + level * 2 * GAS_BINS;
     const int b0 = 2 * threadIdx.x;
-    uint32_t h0[2], h1[2], incl[2];
+    uint32_t h0[2], h1[2], ex[2];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         h0[c] = b0 < bins ? hist[c * GAS_BINS + b0] : 0u;
         h1[c] = b0 + 1 < bins ? hist[c * GAS_BINS + b0 + 1] : 0u;
-        incl[c] = gas_wave_scan32(h0[c] + h1[c]);
-        if (lane == 63) wsum[c][wave] = incl[c];
+        ex[c] = h0[c] + h1[c];
     }
-    __syncthreads();  // (also: every thread has read head[4..7] before any thread writes them below)
+    gsr_block_scan_excl<1024>(ex);  // (its barrier also: every thread has read head[4..7] before any thread writes them below)
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        uint32_t before = 0u;
-#pragma unroll
-        for (int w = 0; w < 16; w++) before += w < wave ? wsum[c][w] : 0u;
-        const uint32_t in = before + incl[c], ex = in - (h0[c] + h1[c]);
+        const uint32_t in = ex[c] + h0[c] + h1[c];
         if (level == 0 && threadIdx.x == 0 && take[c] == 0u) {
             head[4 + c] = 0u;
             head[6 + c] = 0u;
         }
-        if (take[c] > 0u && ex < take[c] && take[c] <= in) {
-            const bool first = ex + h0[c] >= take[c];
+        if (take[c] > 0u && ex[c] < take[c] && take[c] <= in) {
+            const bool first = ex[c] + h0[c] >= take[c];
             head[4 + c] = prefix[c] | ((uint32_t)(first ? b0 : b0 + 1) << shift);
-            head[6 + c] = first ? take[c] - ex : take[c] - ex - h0[c];
+            head[6 + c] = first ? take[c] - ex[c] : take[c] - ex[c] - h0[c];
         }
     }
 }
 
 // ---- ordered compaction --------------------------------------------------------------------------------------------------------
 // per class one 64-bit value: low word = keys below the threshold, high word = keys equal to it (counts <= N < 2^31 each)
-__device__ __forceinline__ unsigned long long gas_wave_scan64(unsigned long long v)
+__device__ __forceinline__ void gas_flag_values(uint8_t f, unsigned long long (&v)[2] /* fg, bg */)
 {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-// exclusive scan of (a, b) over the block's 256 threads; the totals go to *ta / *tb when given
-__device__ __forceinline__ void gas_block_scan2(unsigned long long& a, unsigned long long& b, unsigned long long* ta, unsigned long long* tb)
-{
-    __shared__ unsigned long long wa[GAS_THREADS / 64], wb[GAS_THREADS / 64];
-    const unsigned long long ia = gas_wave_scan64(a), ib = gas_wave_scan64(b);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) { wa[wave] = ia; wb[wave] = ib; }
-    __syncthreads();
-    unsigned long long ba = 0, bb = 0, sa = 0, sb = 0;
-#pragma unroll
-    for (int w = 0; w < GAS_THREADS / 64; w++) {
-        ba += w < wave ? wa[w] : 0ull;
-        bb += w < wave ? wb[w] : 0ull;
-        sa += wa[w];
-        sb += wb[w];
-    }
-    if (ta) *ta = sa;
-    if (tb) *tb = sb;
-    a = ba + ia - a;
-    b = bb + ib - b;
-}
-
-__device__ __forceinline__ void gas_flag_values(uint8_t f, unsigned long long& a, unsigned long long& b)
-{
-    const unsigned long long v = (f & GAS_LT) ? 1ull : (f & GAS_EQ) ? (1ull << 32) : 0ull;
-    a = (f & 3) == GAS_FG ? v : 0ull;
-    b = (f & 3) == GAS_BG ? v : 0ull;
+    const unsigned long long x = (f & GAS_LT) ? 1ull : (f & GAS_EQ) ? (1ull << 32) : 0ull;
+    v[0] = (f & 3) == GAS_FG ? x : 0ull;
+    v[1] = (f & 3) == GAS_BG ? x : 0ull;
 }
 
 __global__ void __launch_bounds__(GAS_THREADS) gas_flag_kernel(int N, uint32_t s_lo, uint32_t s_hi, const uint8_t* __restrict__ cls,
@@ -269,41 +221,20 @@ __global__ void __launch_bounds__(GAS_THREADS) gas_flag_kernel(int N, uint32_t s
         }
         flag[i] = f;
     }
-    unsigned long long a, b, ta, tb;
-    gas_flag_values(f, a, b);
-    gas_block_scan2(a, b, &ta, &tb);
+    unsigned long long v[2], tot[2];
+    gas_flag_values(f, v);
+    gsr_block_scan_excl<GAS_THREADS>(v, tot);
     if (threadIdx.x == 0) {
-        sum_fg[blockIdx.x] = ta;
-        sum_bg[blockIdx.x] = tb;
+        sum_fg[blockIdx.x] = tot[0];
+        sum_bg[blockIdx.x] = tot[1];
     }
 }
 
 __global__ void __launch_bounds__(1024) gas_top_scan_kernel(int nb, unsigned long long* __restrict__ sum_fg, unsigned long long* __restrict__ sum_bg)
 {
-    __shared__ unsigned long long wsum[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int per = (nb + 1023) / 1024, i0 = threadIdx.x * per;
-    unsigned long long* arr[2] = { sum_fg, sum_bg };
-    unsigned long long s[2], incl[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        s[c] = 0;
-        for (int i = 0; i < per; i++) s[c] += i0 + i < nb ? arr[c][i0 + i] : 0ull;
-        incl[c] = gas_wave_scan64(s[c]);
-        if (lane == 63) wsum[c][wave] = incl[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        unsigned long long run = incl[c] - s[c];
-#pragma unroll
-        for (int w = 0; w < 16; w++) run += w < wave ? wsum[c][w] : 0ull;
-        for (int i = 0; i < per && i0 + i < nb; i++) {
-            const unsigned long long v = arr[c][i0 + i];
-            arr[c][i0 + i] = run;
-            run += v;
-        }
-    }
+    unsigned long long* const arr[2] = { sum_fg, sum_bg };
+    unsigned long long total[2];
+    gsr_top_scan(nb, arr, total);
 }
 
 // An anchor is selected when its key is below the threshold, or equal to it and fewer than `take` equal keys of its class come
@@ -316,14 +247,14 @@ __global__ void __launch_bounds__(GAS_THREADS) gas_place_kernel(int N, int max_p
 {
     const long long i = (long long)blockIdx.x * GAS_THREADS + threadIdx.x;
     const uint8_t f = i < N ? flag[i] : (uint8_t)0;
-    unsigned long long a, b;
-    gas_flag_values(f, a, b);
-    gas_block_scan2(a, b, nullptr, nullptr);
+    unsigned long long v[2];
+    gas_flag_values(f, v);
+    gsr_block_scan_excl<GAS_THREADS>(v);
     if (i >= N) return;
     const int c = f & 3;
     bool sel = false;
     if (f & (GAS_LT | GAS_EQ)) {
-        const unsigned long long e = (c == GAS_FG ? base_fg[blockIdx.x] + a : base_bg[blockIdx.x] + b);
+        const unsigned long long e = (c == GAS_FG ? base_fg[blockIdx.x] + v[0] : base_bg[blockIdx.x] + v[1]);
         const uint32_t lt = (uint32_t)e, eq = (uint32_t)(e >> 32), take = head[6 + c - 1];
         sel = (f & GAS_LT) || eq < take;
         const uint32_t pos = lt + min(eq, take);

@@ -28,6 +28,7 @@
 
 #include "gsr_common.h"
 #include "gsr_math.h"
+#include "gsr_scan.h"
 
 #define GSD_F 32        // feat_dim (arguments/__init__.py:50)
 #define GSD_IN 36       // feat + view(3) + dist(1)
@@ -277,18 +278,7 @@ __global__ void __launch_bounds__(GSD_THREADS) gsd_count_kernel(int N, int K, Gs
 __global__ void __launch_bounds__(1024) gsd_scan_kernel(int nblocks, uint32_t* __restrict__ block_sum /* in place -> exclusive */,
                                                         uint32_t* __restrict__ total)
 {
-    __shared__ uint32_t wsum[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int per = (nblocks + 1023) / 1024, i0 = threadIdx.x * per;
-    uint32_t s = 0;
-    for (int i = 0; i < per; i++) s += i0 + i < nblocks ? block_sum[i0 + i] : 0u;
-    const uint32_t incl = gsr_wave_scan_add(s);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - s, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const uint32_t sw = wsum[w]; run += w < wave ? sw : 0u; tot += sw; }
-    for (int i = 0; i < per && i0 + i < nblocks; i++) { const uint32_t v = block_sum[i0 + i]; block_sum[i0 + i] = run; run += v; }
+    const uint32_t tot = gsr_top_scan(nblocks, block_sum);
     if (threadIdx.x == 0) total[0] = tot;
 }
 
@@ -296,15 +286,9 @@ __global__ void __launch_bounds__(1024) gsd_scan_kernel(int nblocks, uint32_t* _
 __global__ void __launch_bounds__(GSD_THREADS) gsd_first_kernel(int N, const uint8_t* __restrict__ count,
                                                                 const uint32_t* __restrict__ block_base, uint32_t* __restrict__ first)
 {
-    __shared__ uint32_t wsum[GSD_THREADS / 64];
     const int n = blockIdx.x * GSD_THREADS + threadIdx.x;
-    const uint32_t c = n < N ? count[n] : 0u;
-    const uint32_t incl = gsr_wave_scan_add(c);
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t run = block_base[blockIdx.x] + incl - c;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run += wsum[w];
-    if (n < N) first[n] = run;
+    const uint32_t excl = gsr_block_scan_excl<GSD_THREADS>(n < N ? (uint32_t)count[n] : 0u);
+    if (n < N) first[n] = block_base[blockIdx.x] + excl;
 }
 
 // ---- pass B: full decode, compacted output ------------------------------------------------------------------------
@@ -1049,27 +1033,19 @@ hipError_t gsd_launch_zero_hidden(int N, int K, const uint8_t* visible_mask, flo
 // counts, the one-block scan above, per-block placement.
 __global__ void __launch_bounds__(256) gsd_rows_count_kernel(int N, const uint8_t* __restrict__ visible_mask, uint32_t* __restrict__ block_sum)
 {
-    __shared__ uint32_t wsum[4];
     const int n = blockIdx.x * 256 + threadIdx.x;
-    const bool v = n < N && visible_mask[n] != 0;
-    const unsigned long long b = __ballot(v);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    uint32_t c;
+    (void)gsr_block_rank<256>(n < N && visible_mask[n] != 0, &c);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = c;
 }
 
 __global__ void __launch_bounds__(256) gsd_rows_place_kernel(int N, const uint8_t* __restrict__ visible_mask, const uint32_t* __restrict__ block_base,
                                                              int32_t* __restrict__ rows)
 {
-    __shared__ uint32_t wsum[4];
-    const int n = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.x * 256 + threadIdx.x;
     const bool v = n < N && visible_mask[n] != 0;
-    const unsigned long long b = __ballot(v);
-    if (lane == 0) wsum[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t base = block_base[blockIdx.x];
-    for (int w = 0; w < wave; w++) base += wsum[w];
-    if (v) rows[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] = n;
+    const uint32_t rank = gsr_block_rank<256>(v);
+    if (v) rows[block_base[blockIdx.x] + rank] = n;
 }
 
 hipError_t gsd_launch_visible_rows(int N, const uint8_t* visible_mask, int32_t* rows, uint32_t* count, uint32_t* block_scratch, hipStream_t stream)

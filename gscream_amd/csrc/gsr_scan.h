@@ -1,0 +1,95 @@
+// gsr_scan.h -- the scans and the ordered compaction ("count, scan, place") of the kernels around the rasterizer: decode,
+// kNN, anchor growth, anchor sampling.  Integer sums only, with one fixed association order per output element.  (The
+// rasterizer's own scans are fused into its hot kernels and stay there: binning.hip, gsr_fwd_order_block.)
+//
+// The block-wide forms keep their per-wave totals in a static LDS array and hold exactly ONE barrier: a kernel that calls
+// the same form a second time needs a __syncthreads() between the two calls (no kernel does so today).  All threads of the
+// block must make the call.
+#pragma once
+#include "gsr_math.h"  // gsr_wave_scan_add(uint32_t): the DPP form
+
+// inclusive wave scan of 64-bit values (DPP moves 32 bits; this is the one shuffle loop)
+__device__ __forceinline__ unsigned long long gsr_wave_scan_add(unsigned long long v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// Exclusive scan over a block of NT threads, in place, of C independent values per thread behind one barrier; the block's
+// totals go to totals[0..C) when given.
+template <int NT, typename T, int C>
+__device__ __forceinline__ void gsr_block_scan_excl(T (&v)[C], T* totals = nullptr)
+{
+    __shared__ T wsum[C][NT / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        incl[c] = gsr_wave_scan_add(v[c]);
+        if (lane == 63) wsum[c][wave] = incl[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        T base = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; w++) { const T sw = wsum[c][w]; base += w < wave ? sw : (T)0; tot += sw; }
+        v[c] = base + incl[c] - v[c];
+        if (totals) totals[c] = tot;
+    }
+}
+template <int NT, typename T>
+__device__ __forceinline__ T gsr_block_scan_excl(T v, T* total = nullptr)
+{
+    T a[1] = { v };
+    gsr_block_scan_excl<NT>(a, total);
+    return a[0];
+}
+
+// Exclusive scan in place of the nb block totals in each of C arrays, by ONE block of 1024 (thread i owns a contiguous run
+// of ceil(nb / 1024) of them); every thread gets the grand totals.
+template <typename T, int C>
+__device__ __forceinline__ void gsr_top_scan(int nb, T* const (&arr)[C], T (&total)[C])
+{
+    const int per = (nb + 1023) / 1024, i0 = threadIdx.x * per;
+    T run[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        run[c] = 0;
+        for (int i = 0; i < per; i++) run[c] += i0 + i < nb ? arr[c][i0 + i] : (T)0;
+    }
+    gsr_block_scan_excl<1024>(run, total);
+#pragma unroll
+    for (int c = 0; c < C; c++)
+        for (int i = 0; i < per && i0 + i < nb; i++) { const T v = arr[c][i0 + i]; arr[c][i0 + i] = run[c]; run[c] += v; }
+}
+template <typename T>
+__device__ __forceinline__ T gsr_top_scan(int nb, T* arr)
+{
+    T* const a[1] = { arr };
+    T total[1];
+    gsr_top_scan(nb, a, total);
+    return total[0];
+}
+
+// Ordered compaction of a flag per thread: the number of set flags of the block's lower threads (a set flag's position
+// among the block's set flags); the block's count goes to *block_count when given.
+template <int NT>
+__device__ __forceinline__ uint32_t gsr_block_rank(bool set, uint32_t* block_count = nullptr)
+{
+    __shared__ uint32_t wsum[NT / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(set);
+    if (lane == 0) wsum[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; w++) { const uint32_t sw = wsum[w]; base += w < wave ? sw : 0u; tot += sw; }
+    if (block_count) *block_count = tot;
+    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}

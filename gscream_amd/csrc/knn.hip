@@ -26,7 +26,7 @@
 #include <float.h>
 #include <stdint.h>
 
-#include "gsr_math.h"
+#include "gsr_scan.h"
 
 #define GSK_BOX 64
 #define GSK_GROUP 256
@@ -95,16 +95,11 @@ __global__ void __launch_bounds__(256) gsk_morton_kernel(int P, int nparts, cons
 __global__ void __launch_bounds__(1024) gsk_bucket_scan_kernel(const uint32_t* __restrict__ bucket_count, uint2* __restrict__ ranges,
                                                                uint32_t* __restrict__ cursor)
 {
-    __shared__ uint32_t wsum[16];
     constexpr int PER = GSK_BUCKETS / 1024;
     uint32_t v[PER], sum = 0;
 #pragma unroll
     for (int k = 0; k < PER; k++) { v[k] = bucket_count[threadIdx.x * PER + k]; sum += v[k]; }
-    const uint32_t incl = gsr_wave_scan_add(sum);
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run += wsum[w];
+    uint32_t run = gsr_block_scan_excl<1024>(sum);
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         ranges[threadIdx.x * PER + k] = make_uint2(run, run + v[k]);

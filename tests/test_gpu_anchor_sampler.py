@@ -45,7 +45,9 @@ CASES = {
     "N63": lambda: (AH.counted_scene(63, 20, 25, seed=2), 2000),
     "N4099": lambda: (AH.counted_scene(4099, 700, 900, seed=3), 300),                      # several workgroups, a ragged tail
     "N4099_random": lambda: (AH.random_scene(4099, 40, 60, seed=4, mask_values=(0.0, 1.0, 0.5, 2.0, -1.0)), 2000),
-    "N200003": lambda: (AH.random_scene(200_003, 64, 96, seed=5, mask_values=(0.0, 1.0, -1.0)), 2000),  # crosses every scan level
+    "N200003": lambda: (AH.random_scene(200_003, 64, 96, seed=5, mask_values=(0.0, 1.0, -1.0)), 2000),  # 782 blocks: one total per top-scan thread
+    # 262 147 anchors = 1025 blocks of 256: the smallest size at which a top-scan thread owns two totals and the last run is ragged
+    "N262147": lambda: (AH.random_scene(262_147, 64, 96, seed=13, mask_values=(0.0, 1.0, -1.0)), 2000),
     "N200003_whole_classes": lambda: (AH.random_scene(200_003, 64, 96, seed=6, rect=(10, 30, 5, 50)), 100_000),
     "cap17_class13": lambda: (AH.counted_scene(2000, 13, 300, seed=7), 17),                # min_num set by a class
     "cap17_class40": lambda: (AH.counted_scene(2000, 40, 300, seed=8), 17),                # min_num set by the cap
@@ -70,7 +72,7 @@ def test_hip_equals_the_torch_path_bit_for_bit(case):
         assert info[1:5] == [2500, 3000, 2000, 1]
     if case == "not_ok":
         assert info[1:5] == [11, 300, 11, 0] and not hip[0].any() and not hip[1].any()
-    if case == "N200003":
+    if case in ("N200003", "N262147"):
         assert info[4] == 1 and info[3] == 2000 and min(info[1], info[2]) > 5000
     if case == "N200003_whole_classes":
         assert info[4] == 1 and info[3] == min(info[1], info[2]) > 2048                   # one side is its whole class

@@ -218,6 +218,34 @@ def test_visible_rows_on_the_device_match_nonzero(N):
         assert bool((rows[n:] == -7).all()), "nothing is written behind the count"
 
 
+@pytest.mark.parametrize("N", [255, 256, 257, 262_144, 262_145])
+def test_decode_count_scan_outputs_against_cumsum(N):
+    """gsr_decode_count's bookkeeping against torch on the call's own `count` and `mask` outputs (integers, compared for equality):
+    count = the mask's row sums, first = the exclusive cumulative sum of count, total = its sum.  Sizes around one block of 256
+    anchors, and 1024 / 1025 blocks: from 1025 on a thread of the one-block scan owns two block totals and the last run is ragged.
+    Default-initialised MLPs on random features keep about half of the offsets, so neither an empty nor a full mask hides the scan."""
+    from gscream_amd import _native
+    from gscream_amd.neural_gaussians import _mlp_tensors
+    K = 10
+    lib = _native.load()
+    dut = DO.Model(N, K, seed=90 + N % 7, dtype=torch.float32).cuda()
+    f32 = lambda t: t.detach().contiguous().float()
+    feat, anchor, campos = f32(dut._anchor_feat), f32(dut.get_anchor), torch.tensor(CAM, device="cuda")
+    t = [_mlp_tensors(m) for m in (dut.get_opacity_mlp, dut.get_uncertainty_mlp, dut.get_color_mlp, dut.get_cov_mlp)]
+    ws = [f32(t[m][i]) for i in range(4) for m in range(4)]
+    warr = (ctypes.c_void_p * 16)(*[w.data_ptr() for w in ws])
+    full = lambda n, v, dt: torch.full((n,), v, dtype=dt, device="cuda")
+    nop, mask, count = full(N * K, 7.0, torch.float32), full(N * K, 77, torch.uint8), full(N, 77, torch.uint8)
+    first, total, scratch = full(N, -7, torch.int32), full(1, -7, torch.int32), full(N // 256 + 2, -7, torch.int32)
+    P = _native.ptr
+    _native.check(lib.gsr_decode_count(N, K, warr, None, None, P(feat), P(anchor), P(campos), P(nop), P(mask), P(count), P(first), P(total),
+                                       P(scratch), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_decode_count")
+    mask, count, first, total = mask.cpu().long(), count.cpu().long(), first.cpu().long(), int(total.item())
+    assert bool((mask <= 1).all()) and torch.equal(count, mask.view(N, K).sum(1)), "count"
+    assert torch.equal(first, torch.cumsum(count, 0) - count), "first"
+    assert total == int(count.sum()) and 0 < total < N * K, ("total", total)
+
+
 def test_absent_upstream_gradients_travel_as_null():
     """A loss that touches only some decode outputs: the others' upstream gradients are None (set_materialize_grads(False)) and
     reach the kernel as NULL pointers instead of zero tensors -- same parameter gradients, bit for bit, as explicit zeros."""
