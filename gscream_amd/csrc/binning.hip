@@ -13,6 +13,7 @@
 // HBM traffic: hist reads rect + mask (16 B/G); table NB*T*4 B written, scanned, read; scatter reads 24 B/G and
 // writes 4 B/instance (the id) + 16 B/G (record tail); sort reads 4 B + a 4-B depth gather and writes 4 B per instance.
 #include "gsr_math.h"
+#include "gsr_scan.h"
 
 typedef unsigned long long u64;
 
@@ -219,71 +220,49 @@ __global__ void __launch_bounds__(GSR_COLSCAN_TILES * GSR_COLSCAN_GROUPS) gsr_ta
     }
 }
 
-// Single block of 1024: exclusive scan of the tile totals -> ranges[t] = [start, end); info = {R, max count}.
-// Thread i owns ceil(T/1024) consecutive tiles; one DPP wave scan + 16 wave totals in LDS.  The counts are loaded ONCE, all loads
-// in flight together (PER = compile-time bound on the tiles per thread): the first version read them in two dependent loops and
-// took 20 us at 8160 tiles -- a chain of memory round trips on a single workgroup (round 4: the banded scatter needs this kernel).
+// The tile scan: exclusive scan of the tile totals -> ranges[t] = [start, end), the frame words every later stage starts from, and
+// info = {R, longest list, instances the occlusion cut-off dropped, 0}.  ONE statement of it for both producers: gsr_tile_scan_kernel
+// (the two-stage forward, images beyond the LDS tile limit) and workgroup 0 of the scatter (the one-call forward).
+struct GsrTileScanOut {
+    uint2* ranges;
+    uint32_t *info, *tile_work, *sorted_len, *need_full;
+    uint32_t* info_host;       // the host's copy of info[0..2], or NULL
+    const uint32_t* occ_drop;  // per-chunk counts of the occlusion cut-off's dropped instances (NULL = off): summed into info[2]
+};
+// By a workgroup of NT threads; start(t, s) also hands tile t's first list position to the caller (the scan alone, for a workgroup that
+// needs only the starts: gsr_block_scan_runs over tile_count).  dropped, longest = two LDS words of the caller's; ndrop (<= 256 <= NT) = entries of occ_drop.
+template <int NT, int PER, typename Start>
+__device__ __forceinline__ void gsr_tile_scan(const int T, const uint32_t* __restrict__ tile_count, const GsrTileScanOut& o, const int ndrop,
+                                              uint32_t& dropped, uint32_t& longest, Start start)
+{
+    if (threadIdx.x == 0) { dropped = 0u; longest = 0u; }
+    __syncthreads();
+    if (o.occ_drop && (int)threadIdx.x < ndrop) { const uint32_t d = o.occ_drop[threadIdx.x]; if (d) atomicAdd(&dropped, d); }
+    uint32_t total;
+    gsr_block_scan_runs<NT, PER>(T, [&](int t) { return tile_count[t]; }, [&](int t, uint32_t s, uint32_t c) {
+        o.ranges[t] = make_uint2(s, s + c);
+        o.tile_work[t] = 0u;  // the forward blend's quadrant wavefronts atomicMax their traversal depth into it
+        o.sorted_len[t] = c;  // fully sorted unless the partial sort of long lists says otherwise
+        o.need_full[t] = 0u;
+        start(t, s);
+    }, &total, &longest);
+    if (threadIdx.x == 0) {  // (the barrier between the atomics and here: the scan's __syncthreads)
+        o.info[0] = total; o.info[1] = longest; o.info[2] = dropped;
+        o.info[3] = 0u;  // quadrant walks that go beyond the first tier of depth segments: counted by the forward blend, read by the backward blend
+        // the host's copy, written straight into its pinned (device-mapped) buffer: no copy kernel in the stream
+        if (o.info_host) { o.info_host[0] = total; o.info_host[1] = longest; o.info_host[2] = dropped; }
+    }
+}
+
+// Single block of 1024.  Thread i owns ceil(T/1024) consecutive tiles; one DPP wave scan + 16 wave totals in LDS.  The counts are loaded
+// ONCE, all loads in flight together (PER = compile-time bound on the tiles per thread): the first version read them in two dependent
+// loops and took 20 us at 8160 tiles -- a chain of memory round trips on a single workgroup (round 4: the banded scatter needs this kernel).
 // (PER = 0: no register copy, the counts are read again in the second loop -- images beyond the LDS tile limit, any T)
 template <int PER>
-__global__ void __launch_bounds__(1024) gsr_tile_scan_kernel(int T, const uint32_t* __restrict__ tile_count,
-                                                             uint2* __restrict__ ranges, uint32_t* __restrict__ info,
-                                                             uint32_t* __restrict__ tile_work, uint32_t* __restrict__ sorted_len,
-                                                             uint32_t* __restrict__ need_full, uint32_t* __restrict__ info_host,
-                                                             const uint32_t* __restrict__ occ_drop, int ndrop)
+__global__ void __launch_bounds__(1024) gsr_tile_scan_kernel(int T, const uint32_t* __restrict__ tile_count, const GsrTileScanOut out, int ndrop)
 {
-    __shared__ uint32_t wsum[16], wmax[16];
-    __shared__ uint32_t drop_total;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) drop_total = 0u;
-    __syncthreads();
-    if (occ_drop && (int)threadIdx.x < ndrop) { const uint32_t d = occ_drop[threadIdx.x]; if (d) atomicAdd(&drop_total, d); }  // ndrop <= 256
-    const int per = (T + 1023) / 1024, t0 = threadIdx.x * per;  // per <= PER
-    uint32_t v[PER > 0 ? PER : 1];
-    uint32_t sum = 0, mx = 0;
-    if (PER > 0) {
-#pragma unroll
-        for (int i = 0; i < PER; i++) v[i] = (i < per && t0 + i < T) ? tile_count[t0 + i] : 0u;
-#pragma unroll
-        for (int i = 0; i < PER; i++) { sum += v[i]; mx = max(mx, v[i]); }
-    } else {
-        for (int i = 0; i < per; i++) {
-            const uint32_t c = t0 + i < T ? tile_count[t0 + i] : 0u;
-            sum += c;
-            mx = max(mx, c);
-        }
-    }
-    const uint32_t incl = gsr_wave_scan_add(sum);
-    mx = gsr_wave_scan_max(mx);
-    if (lane == 63) { wsum[wave] = incl; wmax[wave] = mx; }
-    __syncthreads();
-    uint32_t run = incl - sum, total = 0, gmax = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const uint32_t sw = wsum[w];
-        run += w < wave ? sw : 0u;
-        total += sw;
-        gmax = max(gmax, wmax[w]);
-    }
-    auto emit = [&](const int t, const uint32_t c) {
-        ranges[t] = make_uint2(run, run + c);
-        tile_work[t] = 0u;  // the forward blend's quadrant wavefronts atomicMax their traversal depth into it
-        sorted_len[t] = c;  // fully sorted unless the partial sort of long lists says otherwise
-        need_full[t] = 0u;
-        run += c;
-    };
-    if (PER > 0) {
-#pragma unroll
-        for (int i = 0; i < PER; i++)
-            if (i < per && t0 + i < T) emit(t0 + i, v[i]);
-    } else {
-        for (int i = 0; i < per && t0 + i < T; i++) emit(t0 + i, tile_count[t0 + i]);
-    }
-    if (threadIdx.x == 0) {
-        info[0] = total; info[1] = gmax; info[2] = drop_total;  // (the barrier between the atomics and here: the scan's __syncthreads)
-        info[3] = 0u;  // quadrant walks that go beyond the first tier of depth segments: counted by the forward blend, read by the backward blend
-        // the host's copy, written straight into its pinned (device-mapped) buffer: no copy kernel in the stream
-        if (info_host) { info_host[0] = total; info_host[1] = gmax; info_host[2] = drop_total; }
-    }
+    __shared__ uint32_t dropped, longest;
+    gsr_tile_scan<1024, PER>(T, tile_count, out, ndrop, dropped, longest, [](int, uint32_t) {});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -293,13 +272,11 @@ __global__ void __launch_bounds__(1024) gsr_tile_scan_kernel(int T, const uint32
 // GLOBAL = true (more tiles than LDS holds): the per-tile cursors are a global array initialised to the segment
 // starts (`table` then points at it), claimed with agent-scope atomics.
 // When the tile scan is folded into this kernel (the one-call forward: the host does not need R before stage 2 is enqueued):
-// every workgroup scans the tile totals for its own cursors, workgroup 0 also writes what gsr_tile_scan_kernel writes.
+// every workgroup scans the tile totals for its own cursors, workgroup 0 runs the whole gsr_tile_scan.
 struct GsrFusedScan {
     const uint32_t* tile_count;  // null = not folded in: `ranges` was written by gsr_tile_scan_kernel
-    uint2* ranges;
-    uint32_t *info, *tile_work, *sorted_len, *need_full, *info_host;
-    const uint32_t* occ_drop;  // per-chunk counts of the occlusion cut-off's dropped instances (NULL = off): summed into info[2]
     const uint32_t* tile_group;  // totals of the tile groups of GSR_COLSCAN_TILES tiles (column scan)
+    GsrTileScanOut out;
 };
 // BANDED = false compiles the band arithmetic away (nbands = 1: the plain launch, e.g. config 2, keeps its round-3 code: with the
 // run-time form it was 2 us slower).
@@ -313,12 +290,12 @@ __global__ void __launch_bounds__(GSR_HIST_THREADS) gsr_scatter_kernel(
     const int nbands = BANDED ? nbands_arg : 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t cursor_lds[];
     uint32_t* cursor = GLOBAL ? const_cast<uint32_t*>(table) : cursor_lds;
-    __shared__ uint32_t heads_all[GSR_HIST_THREADS];
-    __shared__ uint32_t wsum[GSR_HIST_THREADS / 64];
-    __shared__ uint32_t wsum4[4][GSR_HIST_THREADS / 64];
-    __shared__ uint32_t chunk_first;
+    constexpr int NT = GSR_HIST_THREADS;  // = blockDim.x
+    __shared__ uint32_t heads_all[NT];
+    __shared__ uint32_t chunk_first;  // first gradient slot of the chunk
+    __shared__ uint32_t band_total;   // instances of this (chunk, band): known after the scan of the per-tile counts below
     volatile uint32_t* heads = heads_all + (threadIdx.x & ~63u);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     // workgroup b runs on XCD b % 8: consecutive CHUNKS go to one XCD, so that the runs two neighbouring chunks write into a
     // tile segment (they share a 32-byte sector at their border) meet in the same L2
     // BANDED form (round 4; nbands > 1): images with so many tiles / instances that a chunk's keys do not fit the staging buffer
@@ -343,73 +320,25 @@ __global__ void __launch_bounds__(GSR_HIST_THREADS) gsr_scatter_kernel(
     uint32_t* gbase = cursor_lds + 2 * (size_t)TB;
     u64* skey = reinterpret_cast<u64*>(cursor_lds + 3 * (size_t)TB + ((3 * (size_t)TB) & 1));
     uint16_t* stile = reinterpret_cast<uint16_t*>(skey + stage_cap);
-    __shared__ uint32_t band_total;  // instances of this (chunk, band): known after the scan of the per-tile counts below
     const bool may_stage = !GLOBAL && stage_cap > 0u && TB <= 65535;  // block-uniform
     bool staged = false;
     const bool fused = !GLOBAL && fs.tile_count != nullptr;  // block-uniform
-    if (BANDED && fused && blockIdx.x != 0) {
-        // banded: only this band's tile starts are needed.  First list position of the band = the totals of the tile groups in front
-        // of it (T / 64 words from the column scan) + an exclusive scan over the tiles from the band's group boundary on.
-        const int g0 = t_lo / GSR_COLSCAN_TILES, ts = g0 * GSR_COLSCAN_TILES, n = t_lo + TB - ts;
-        uint32_t pv = 0u;
-        for (int g = threadIdx.x; g < g0; g += blockDim.x) pv += fs.tile_group[g];
-        const int per = (n + (int)blockDim.x - 1) / (int)blockDim.x, t0 = ts + (int)threadIdx.x * per;
-        uint32_t sum = 0;
-        for (int i = 0; i < per; i++) sum += t0 + i < ts + n ? fs.tile_count[t0 + i] : 0u;
-        const uint32_t incl = gsr_wave_scan_add(sum), gincl = gsr_wave_scan_add(pv);
-        if (lane == 63) { wsum[wave] = incl; wsum4[0][wave] = gincl; }
-        __syncthreads();
-        uint32_t run = incl - sum;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) run += (w < wave ? wsum[w] : 0u) + wsum4[0][w];
-        for (int i = 0; i < per; i++) {
-            if (t0 + i >= ts + n) break;
-            if (t0 + i >= t_lo) cursor[t0 + i - t_lo] = run;
-            run += fs.tile_count[t0 + i];
-        }
-        __syncthreads();
-    } else if (fused) {
-        // tile starts = exclusive scan of the tile totals, left in cursor[] for the initialisation below (thread i owns
-        // ceil(T / blockDim) consecutive tiles, like the staged scan further down)
-        const int per = (T + (int)blockDim.x - 1) / (int)blockDim.x, t0 = (int)threadIdx.x * per;
-        uint32_t sum = 0, mx = 0;
-        for (int i = 0; i < per; i++) {
-            const uint32_t v = t0 + i < T ? fs.tile_count[t0 + i] : 0u;
-            sum += v;
-            mx = max(mx, v);
-        }
-        const uint32_t incl = gsr_wave_scan_add(sum);
-        mx = gsr_wave_scan_max(mx);
-        if (lane == 63) { wsum[wave] = incl; wsum4[0][wave] = mx; }
-        __syncthreads();
-        uint32_t run = incl - sum, total = 0, gmax = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
-            const uint32_t sw = wsum[w];
-            run += w < wave ? sw : 0u;
-            total += sw;
-            gmax = max(gmax, wsum4[0][w]);
-        }
-        for (int i = 0; i < per; i++) {
-            if (t0 + i >= T) break;
-            const uint32_t v = fs.tile_count[t0 + i];
-            if (t0 + i >= t_lo && t0 + i < t_lo + TB) cursor[t0 + i - t_lo] = run;  // (this workgroup's band of tiles)
-            if (blockIdx.x == 0) {  // what gsr_tile_scan_kernel writes
-                fs.ranges[t0 + i] = make_uint2(run, run + v);
-                fs.tile_work[t0 + i] = 0u;
-                fs.sorted_len[t0 + i] = v;
-                fs.need_full[t0 + i] = 0u;
-            }
-            run += v;
-        }
-        if (blockIdx.x == 0) {
-            if (threadIdx.x == 0) chunk_first = 0u;  // (borrowed: reset below before its real use)
-            __syncthreads();
-            if (fs.occ_drop && (int)threadIdx.x < nchunks) { const uint32_t d = fs.occ_drop[threadIdx.x]; if (d) atomicAdd(&chunk_first, d); }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const uint32_t dropped = chunk_first;
-                fs.info[0] = total; fs.info[1] = gmax; fs.info[2] = dropped; fs.info[3] = 0u;  // ([3]: see gsr_tile_scan_kernel)
-                if (fs.info_host) { fs.info_host[0] = total; fs.info_host[1] = gmax; fs.info_host[2] = dropped; }
-            }
+    if (fused) {
+        // tile starts = exclusive scan of the tile totals, left in cursor[] for the initialisation below
+        if (blockIdx.x == 0) {  // (the two LDS words: borrowed, both are set below before their real use)
+            gsr_tile_scan<NT, 0>(T, fs.tile_count, fs.out, nchunks, chunk_first, band_total, [&](int t, uint32_t s) {
+                if (t >= t_lo && t < t_lo + TB) cursor[t - t_lo] = s;  // (this workgroup's band of tiles)
+            });
+        } else if (!BANDED) {
+            gsr_block_scan_runs<NT, 0>(T, [&](int t) { return fs.tile_count[t]; }, [&](int t, uint32_t s, uint32_t) { cursor[t] = s; });
+        } else {
+            // banded: only this band's tile starts are needed.  First list position of the band = the totals of the tile groups in front
+            // of it (T / 64 words from the column scan) + an exclusive scan over the tiles from the band's group boundary on: ONE scan
+            // over the g0 group totals followed by those tiles' totals.
+            const int g0 = t_lo / GSR_COLSCAN_TILES, first = g0 * (GSR_COLSCAN_TILES - 1);  // entry j >= g0 is tile j + first
+            gsr_block_scan_runs<NT, 0>(g0 + t_lo + TB - g0 * GSR_COLSCAN_TILES,
+                                       [&](int j) { return j < g0 ? fs.tile_group[j] : fs.tile_count[j + first]; },
+                                       [&](int j, uint32_t s, uint32_t) { if (j + first >= t_lo) cursor[j + first - t_lo] = s; });
         }
         __syncthreads();
     }
@@ -448,23 +377,13 @@ __global__ void __launch_bounds__(GSR_HIST_THREADS) gsr_scatter_kernel(
     if (may_stage) {
         // exclusive scan of the (chunk, band)'s per-tile counts -> local offsets (thread i owns ceil(TB / blockDim) consecutive tiles);
         // the total decides whether the keys fit the staging buffer
-        const int per = (TB + (int)blockDim.x - 1) / (int)blockDim.x, t0 = (int)threadIdx.x * per;
-        uint32_t sum = 0;
-        for (int i = 0; i < per; i++) sum += t0 + i < TB ? loff[t0 + i] : 0u;
-        const uint32_t incl = gsr_wave_scan_add(sum);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - sum, tot = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) { const uint32_t sw = wsum[w]; tot += sw; run += w < wave ? sw : 0u; }
-        if (threadIdx.x == 0) band_total = tot;
+        uint32_t tot;
+        gsr_block_scan_runs<NT, 0>(TB, [&](int t) { return loff[t]; }, [&](int t, uint32_t s, uint32_t) {
+            loff[t] = s;
+            cursor[t] = tot <= stage_cap ? s : gbase[t];  // the staging cursor of the tile, or (too many keys) its global cursor
+        }, &tot);
         staged = tot <= stage_cap;  // block-uniform
-        for (int i = 0; i < per; i++) {
-            if (t0 + i >= TB) break;
-            const uint32_t v = loff[t0 + i];
-            loff[t0 + i] = run;
-            cursor[t0 + i] = staged ? run : gbase[t0 + i];  // the staging cursor of the tile, or (too many keys) its global cursor
-            run += v;
-        }
+        if (threadIdx.x == 0) band_total = tot;
         __syncthreads();
     }
     // first gradient slot of the chunk = instances of all earlier chunks
@@ -496,25 +415,15 @@ __global__ void __launch_bounds__(GSR_HIST_THREADS) gsr_scatter_kernel(
         // (blend backward, gauss_bwd).  Same count as the enumeration below by construction.  The four sub-trips' block scans
         // share ONE pair of barriers (wave totals of all four in LDS at once) instead of taking a pair each.
         if (offsets && band == 0) {  // (block-uniform; NULL = inference forward: nobody will ask for gradient slots)
-            uint32_t cnt[U], incl[U];
+            uint32_t cnt[U], tot[U];
 #pragma unroll
-            for (int k = 0; k < U; k++) {
-                cnt[k] = gsr_rect_count(rcs[k], mks[k]);
-                incl[k] = gsr_wave_scan_add(cnt[k]);
-                if (lane == 63) wsum4[k][wave] = incl[k];
-            }
-            __syncthreads();
+            for (int k = 0; k < U; k++) cnt[k] = gsr_rect_count(rcs[k], mks[k]);
+            gsr_block_scan_excl<NT, uint32_t, U, true>(cnt, tot);  // (LOOP: the wave totals read in a loop, as the hand-written form did)
 #pragma unroll
             for (int k = 0; k < U; k++) {
                 const int g = gb + k * blockDim.x;
-                uint32_t before = 0, tot = 0;
-                for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
-                    const uint32_t sw = wsum4[k][w];
-                    tot += sw;
-                    before += w < wave ? sw : 0u;
-                }
-                if (g < hi) offsets[g] = carry + before + incl[k] - cnt[k];
-                carry += tot;
+                if (g < hi) offsets[g] = carry + cnt[k];
+                carry += tot[k];
             }
             __syncthreads();  // (the next trip rewrites the wave totals)
         }
@@ -687,6 +596,24 @@ __device__ __forceinline__ void gsr_sort_lds_fused(u64* k, const uint32_t n, con
     }
 }
 
+// Block-wide minimum and maximum of the threads' (mn, mx), in place; red[2 NT / 64].  Holds one barrier.
+template <int NT>
+__device__ __forceinline__ void gsr_block_minmax(u64& mn, u64& mx, u64* red)
+{
+    constexpr int NW = NT / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, (u64)__shfl_xor((unsigned long long)mn, d, 64));
+        mx = max(mx, (u64)__shfl_xor((unsigned long long)mx, d, 64));
+    }
+    if (lane == 0) { red[wave] = mn; red[NW + wave] = mx; }
+    __syncthreads();
+    mn = red[0]; mx = red[NW];
+#pragma unroll
+    for (int w = 1; w < NW; w++) { mn = min(mn, red[w]); mx = max(mx, red[NW + w]); }
+}
+
 // Counting sort of one tile list held in registers (n <= NT * KPT keys, thread t owns keys t, t + NT, ...), two levels, O(n)
 // instead of the bitonic network's n log^2 n / 2 compare-exchanges of 5 VALU operations each (2048 keys: 66 stages).
 // Level 1: the 64-bit keys (depth bits, id) are spread over 4 * NT equal-width buckets of their own range (LDS atomics, one scan).
@@ -706,26 +633,18 @@ __device__ __forceinline__ void gsr_sort_lds_fused(u64* k, const uint32_t n, con
 // NT threads, KPT keys per thread in registers (n <= NT * KPT), 4 * NT buckets (thread t owns buckets 4t .. 4t+3).
 template <int NT, int KPT>
 __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint32_t n, u64* k, uint32_t* offs /*[4 NT]*/,
-                                                 u64* red /*[2 NT / 64]*/, uint32_t* wtot /*[NT / 64 + 2]*/)
+                                                 u64* red /*[2 NT / 64]*/, uint32_t* wtot /*[1]: the sum of the squared sub-bucket counts*/)
 {
-    constexpr int NW = NT / 64, NB = 4 * NT, LOGNB = NT == 256 ? 10 : 12;
+    constexpr int NB = 4 * NT, LOGNB = NT == 256 ? 10 : 12;
     static_assert(NT == 256 || NT == 1024, "bucket count = 4 NT must match LOGNB");
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    u64 mn = ~0ull, mx = 0ull;
+    const int t = threadIdx.x;
+    u64 kmin = ~0ull, kmax = 0ull;
 #pragma unroll
     for (int j = 0; j < KPT; j++)
-        if ((uint32_t)(t + NT * j) < n) { mn = min(mn, v[j]); mx = max(mx, v[j]); }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        mn = min(mn, (u64)__shfl_xor((unsigned long long)mn, d, 64));
-        mx = max(mx, (u64)__shfl_xor((unsigned long long)mx, d, 64));
-    }
-    if (lane == 0) { red[wave] = mn; red[NW + wave] = mx; }
+        if ((uint32_t)(t + NT * j) < n) { kmin = min(kmin, v[j]); kmax = max(kmax, v[j]); }
     for (int i = t; i < NB; i += NT) offs[i] = 0u;
-    __syncthreads();
-    u64 kmin = red[0], kmax = red[NW];
-#pragma unroll
-    for (int w = 1; w < NW; w++) { kmin = min(kmin, red[w]); kmax = max(kmax, red[NW + w]); }
+    if (t == 0) wtot[0] = 0u;
+    gsr_block_minmax<NT>(kmin, kmax, red);
     const u64 span = kmax - kmin;
     const int shift = span < (u64)NB ? 0 : (64 - __builtin_clzll(span)) - LOGNB;  // (key - kmin) >> shift < NB
     uint32_t b[KPT];
@@ -735,15 +654,8 @@ __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint
         if ((uint32_t)(t + NT * j) < n) atomicAdd(&offs[b[j]], 1u);
     }
     __syncthreads();
-    // exclusive scan of the bucket counts (thread t owns buckets 4t .. 4t+3)
-    const uint32_t h0 = offs[4 * t], h1 = offs[4 * t + 1], h2 = offs[4 * t + 2], h3 = offs[4 * t + 3];
-    const uint32_t mine = h0 + h1 + h2 + h3;
-    const uint32_t incl = gsr_wave_scan_add(mine);
-    if (lane == 63) { wtot[wave] = incl; wtot[NW] = 0u; wtot[NW + 1] = 0u; }
-    __syncthreads();
-    uint32_t run = incl - mine;
-    for (int w = 0; w < wave; w++) run += wtot[w];
-    offs[4 * t] = run; offs[4 * t + 1] = run + h0; offs[4 * t + 2] = run + h0 + h1; offs[4 * t + 3] = run + h0 + h1 + h2;
+    // exclusive scan of the bucket counts in place (thread t owns buckets 4t .. 4t+3)
+    gsr_block_scan_runs<NT, 4>(NB, [&](int i) { return offs[i]; }, [&](int i, uint32_t s, uint32_t) { offs[i] = s; });
     __syncthreads();
     // ---- second level: 16-bit sub-bucket counters, two per word of offs[] (free once every key knows its sub-bucket) ----
     uint32_t idx[KPT];
@@ -775,19 +687,16 @@ __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint
         }
 #pragma unroll
         for (int e = 0; e < 8; e++) { loc += c2[e]; sq += c2[e] * c2[e]; }
-        const uint32_t incl2 = gsr_wave_scan_add(loc);
         const uint32_t sqw = gsr_wave_scan_add(sq);
-        if (lane == 63) { wtot[wave] = incl2; atomicAdd(&wtot[NW + 1], sqw); }
-        __syncthreads();
-        if (!fits2 || wtot[NW + 1] > 24u * n) {  // keys equal in every bit both levels look at: the network (block-uniform)
+        if ((t & 63) == 63) atomicAdd(&wtot[0], sqw);
+        uint32_t run2 = gsr_block_scan_excl<NT>(loc);
+        if (!fits2 || wtot[0] > 24u * n) {  // keys equal in every bit both levels look at: the network (block-uniform)
 #pragma unroll
             for (int j = 0; j < KPT; j++)
                 if ((uint32_t)(t + NT * j) < n) k[GSR_PAD(t + NT * j)] = v[j];
             __syncthreads();
             return false;
         }
-        uint32_t run2 = incl2 - loc;
-        for (int w = 0; w < wave; w++) run2 += wtot[w];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const uint32_t lo16 = run2, hi16 = run2 + c2[2 * e];
@@ -824,6 +733,20 @@ __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint
     return true;
 }
 
+// One list from registers to its sorted ids at dst[0..n): the bucket sort, the fused network when its keys are clustered.
+// (in_regs = false: the list is longer than NT * KPT and already lies at keys[GSR_PAD(i)], for the network)
+template <int NT, int KPT>
+__device__ __forceinline__ void gsr_sort_list(const u64 (&v)[KPT], const uint32_t n, u64* keys, uint32_t* offs, u64* red, uint32_t* wtot,
+                                              uint32_t* __restrict__ dst, const bool in_regs = true)
+{
+    if (in_regs && gsr_sort_buckets<NT, KPT>(v, n, keys, offs, red, wtot)) {  // n, in_regs are block-uniform
+        for (uint32_t i = threadIdx.x; i < n; i += NT) dst[i] = (uint32_t)keys[i];
+    } else {
+        if (n > 1) gsr_sort_lds_fused(keys, n, NT);
+        for (uint32_t i = threadIdx.x; i < n; i += NT) dst[i] = (uint32_t)keys[GSR_PAD(i)];
+    }
+}
+
 // LDS variant for lo < n <= hi (dynamic LDS = 8 * GSR_PAD(hi) bytes).  NT = 256 threads (8 keys each) for the lists up
 // to 2048, 1024 threads (16 keys each) for the class up to 16384.
 template <int NT>
@@ -839,7 +762,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
     extern __shared__ __attribute__((aligned(16))) u64 keys[];
     __shared__ uint32_t offs[4 * NT];
     __shared__ u64 red[2 * NT / 64];
-    __shared__ uint32_t wtot[NT / 64 + 2];
+    __shared__ uint32_t wtot[1];
     if (only_flagged && !only_flagged[blockIdx.x]) return;  // fix-up pass: only the tiles whose sorted prefix ran out
     const uint2 rg = ranges[blockIdx.x];
     const uint32_t n = rg.y - rg.x;
@@ -849,24 +772,19 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
     // the tile ranges partition [0, R): each block clears its share of the written-slot flags for the backward
     if (slot_written) for (uint32_t i = threadIdx.x; i < n; i += NT) slot_written[rg.x + i] = 0;
     // the scatter left the tile's 64-bit keys (depth bits, Gaussian id) in its segment of seg_keys
-    if (n <= (uint32_t)(NT * KPT)) {
-        u64 v[KPT];
+    const bool in_regs = n <= (uint32_t)(NT * KPT);
+    u64 v[KPT];
+    if (in_regs) {
 #pragma unroll
         for (int j = 0; j < KPT; j++) {
             const uint32_t i = threadIdx.x + (uint32_t)NT * j;
             v[j] = i < n ? seg_keys[rg.x + i] : 0ull;
         }
-        if (gsr_sort_buckets<NT, KPT>(v, n, keys, offs, red, wtot)) {
-            for (uint32_t i = threadIdx.x; i < n; i += NT) point_list[rg.x + i] = (uint32_t)keys[i];
-            if (sorted_len && threadIdx.x == 0) sorted_len[blockIdx.x] = n;
-            return;
-        }
     } else {
         for (uint32_t i = threadIdx.x; i < n; i += NT) keys[GSR_PAD(i)] = seg_keys[rg.x + i];
         __syncthreads();
     }
-    gsr_sort_lds_fused(keys, n, NT);
-    for (uint32_t i = threadIdx.x; i < n; i += NT) point_list[rg.x + i] = (uint32_t)keys[GSR_PAD(i)];
+    gsr_sort_list<NT, KPT>(v, n, keys, offs, red, wtot, point_list + rg.x, in_regs);  // (!in_regs: v is not read, the network takes keys[])
     if (sorted_len && threadIdx.x == 0) sorted_len[blockIdx.x] = n;
 }
 
@@ -887,11 +805,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
     __shared__ __attribute__((aligned(16))) u64 keys[GSR_PAD(GSR_NEAR_CAP) + 1];
     __shared__ uint32_t hist[1024];
     __shared__ u64 red[8];
-    __shared__ uint32_t s_pick, s_near, s_far;
+    __shared__ uint32_t s_pick, s_near, s_far, wtot[1];
     const uint2 rg = ranges[blockIdx.x];
     const uint32_t n = rg.y - rg.x;
     if (rg.y > capacity) return;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     const u64* src = seg_keys + rg.x;
     if (slot_written) for (uint32_t i = t; i < n; i += 256) slot_written[rg.x + i] = 0;
     if (n <= GSR_NEAR_CAP) {
@@ -901,28 +819,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
         u64 v[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) v[j] = (uint32_t)(t + 256 * j) < n ? src[t + 256 * j] : 0ull;
-        __shared__ uint32_t wtot0[6];
-        if (gsr_sort_buckets<256, 8>(v, n, keys, hist, red, wtot0)) {
-            for (uint32_t i = t; i < n; i += 256) point_list[rg.x + i] = (uint32_t)keys[i];
-        } else {
-            if (n > 1) gsr_sort_lds_fused(keys, n, 256);
-            for (uint32_t i = t; i < n; i += 256) point_list[rg.x + i] = (uint32_t)keys[GSR_PAD(i)];
-        }
+        gsr_sort_list<256, 8>(v, n, keys, hist, red, wtot, point_list + rg.x);
         return;  // sorted_len[tile] = n already (tile scan)
     }
     // pass A: key range
-    u64 mn = ~0ull, mx = 0ull;
-    for (uint32_t i = t; i < n; i += 256) { const u64 k = src[i]; mn = min(mn, k); mx = max(mx, k); }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        mn = min(mn, (u64)__shfl_xor((unsigned long long)mn, d, 64));
-        mx = max(mx, (u64)__shfl_xor((unsigned long long)mx, d, 64));
-    }
-    if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; }
+    u64 kmin = ~0ull, kmax = 0ull;
+    for (uint32_t i = t; i < n; i += 256) { const u64 k = src[i]; kmin = min(kmin, k); kmax = max(kmax, k); }
     for (int i = t; i < 1024; i += 256) hist[i] = 0u;
     if (t == 0) { s_pick = 0u; s_near = 0u; s_far = 0u; }
-    __syncthreads();
-    const u64 kmin = min(min(red[0], red[1]), min(red[2], red[3])), kmax = max(max(red[4], red[5]), max(red[6], red[7]));
+    gsr_block_minmax<256>(kmin, kmax, red);
     const u64 span = kmax - kmin;
     const int shift = span < 1024ull ? 0 : (64 - __builtin_clzll(span)) - 10;  // (k - kmin) >> shift < 1024
     // pass B: histogram of the key buckets
@@ -930,21 +835,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
     __syncthreads();
     // the last bucket boundary with <= GSR_NEAR_CAP keys in front of it: thread t owns buckets 4t .. 4t+3
     {
-        const uint32_t h0 = hist[4 * t], h1 = hist[4 * t + 1], h2 = hist[4 * t + 2], h3 = hist[4 * t + 3];
-        const uint32_t mine = h0 + h1 + h2 + h3;
-        const uint32_t incl = gsr_wave_scan_add(mine);
-        __shared__ uint32_t wtot[4];
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - mine;
-        for (int w = 0; w < wave; w++) run += wtot[w];
-        const uint32_t hh[4] = { h0, h1, h2, h3 };
         uint32_t best = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            run += hh[j];
-            if (run <= GSR_NEAR_CAP) best = ((uint32_t)(4 * t + j + 1) << 12) | run;  // (bucket + 1, keys up to it)
-        }
+        gsr_block_scan_runs<256, 4>(1024, [&](int i) { return hist[i]; }, [&](int i, uint32_t s, uint32_t c) {
+            if (s + c <= GSR_NEAR_CAP) best = ((uint32_t)(i + 1) << 12) | (s + c);  // (bucket + 1, keys up to it)
+        });
         if (best) atomicMax(&s_pick, best);
     }
     __syncthreads();
@@ -968,13 +862,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
 #pragma unroll
         for (int j = 0; j < 8; j++) v[j] = (uint32_t)(t + 256 * j) < m ? keys[GSR_PAD(t + 256 * j)] : 0ull;
         __syncthreads();
-        __shared__ uint32_t wtot2[6];
-        if (gsr_sort_buckets<256, 8>(v, m, keys, hist, red, wtot2)) {  // m is block-uniform
-            for (uint32_t i = t; i < m; i += 256) point_list[rg.x + i] = (uint32_t)keys[i];
-        } else {
-            if (m > 1) gsr_sort_lds_fused(keys, m, 256);
-            for (uint32_t i = t; i < m; i += 256) point_list[rg.x + i] = (uint32_t)keys[GSR_PAD(i)];
-        }
+        gsr_sort_list<256, 8>(v, m, keys, hist, red, wtot, point_list + rg.x);  // m is block-uniform
     }
     if (t == 0) sorted_len[blockIdx.x] = m;
 }
@@ -1005,6 +893,19 @@ __global__ void __launch_bounds__(1024) gsr_tile_sort_global_kernel(const uint2*
 // ---------------------------------------------------------------------------------------------
 // Dynamic LDS beyond 64 KiB needs a one-time opt-in per kernel and device (kept out of the per-call path: a
 // hipFuncSetAttribute between the stage-1 read-back and the stage-2 launches is exposed GPU idle time).
+constexpr size_t GSR_BIG_LDS = 160 * 1024 - 8192;  // static LDS: hist / scatter 2 KiB, tile sort 4.2 KiB (bucket offsets)
+
+// The scatter's dynamic LDS for a band of tb tiles: the three per-tile arrays (fixed) + a staging buffer of 10 B per instance, as
+// much as the CU has left (stage_cap instances; 0 = no room worth staging in).  gsr_scatter_bands chooses the band count by it
+// and gsr_launch_scatter provides it.
+struct GsrScatterLds { size_t fixed, stage_cap; };
+static GsrScatterLds gsr_scatter_lds(size_t tb)
+{
+    const size_t budget = GSR_BIG_LDS - 1024;  // static arrays of the kernel: ~4.3 KiB
+    const size_t fixed = gsr_align(tb * 12 + 8);
+    return { fixed, budget > fixed + 4096 ? (budget - fixed) / 10 : 0 };
+}
+
 static hipError_t gsr_allow_big_lds()
 {
     static thread_local uint64_t done_mask = 0;  // one bit per device: switching devices re-issues nothing
@@ -1012,7 +913,7 @@ static hipError_t gsr_allow_big_lds()
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64 && ((done_mask >> dev) & 1)) return hipSuccess;
-    const int big = 160 * 1024 - 8192;  // static LDS: hist / scatter 2 KiB, tile sort 4.2 KiB (bucket offsets)
+    const int big = (int)GSR_BIG_LDS;
     e = hipFuncSetAttribute((const void*)gsr_tile_hist_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
     // (the occlusion variant has 8 KiB more static LDS -- the per-lane dropped-tile masks -- and needs 5 B per tile up to GSR_OCC_MAX_TILES)
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gsr_tile_hist_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big - 16384);
@@ -1021,6 +922,11 @@ static hipError_t gsr_allow_big_lds()
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gsr_tile_sort_lds_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 17408);  // 16.9 KiB static: 4096 bucket offsets + scan scratch
     if (e == hipSuccess && dev >= 0 && dev < 64) done_mask |= 1ull << dev;
     return e;
+}
+
+static GsrTileScanOut gsr_tile_scan_out(const GsrImage& image, uint32_t* info_host, bool occlusion_cut)
+{
+    return { image.ranges, image.info, image.tile_work, image.sorted_len, image.need_full, info_host, occlusion_cut ? image.occ_drop : nullptr };
 }
 
 hipError_t gsr_launch_count(const GsrFrame& f, uint32_t* info_host_mapped, bool defer_tile_scan, bool occlusion_cut,
@@ -1063,10 +969,8 @@ hipError_t gsr_launch_count(const GsrFrame& f, uint32_t* info_host_mapped, bool 
     if (!(defer_tile_scan && T <= GSR_MAX_TILES_LDS))
     {
         const int per = (T + 1023) / 1024;
-#define GSR_TILE_SCAN(N)                                                                                                       \
-        hipLaunchKernelGGL(gsr_tile_scan_kernel<N>, dim3(1), dim3(1024), 0, stream, T, image.tile_count, image.ranges, image.info, \
-                           image.tile_work, image.sorted_len, image.need_full, info_host_mapped,                                   \
-                           occlusion_cut ? (const uint32_t*)image.occ_drop : (const uint32_t*)nullptr, nchunks)
+        const GsrTileScanOut out = gsr_tile_scan_out(image, info_host_mapped, occlusion_cut);
+#define GSR_TILE_SCAN(N) hipLaunchKernelGGL(gsr_tile_scan_kernel<N>, dim3(1), dim3(1024), 0, stream, T, image.tile_count, out, nchunks)
         if (per <= 4) GSR_TILE_SCAN(4);
         else if (per <= 12) GSR_TILE_SCAN(12);
         else if (per <= 36) GSR_TILE_SCAN(36);
@@ -1085,13 +989,12 @@ int gsr_scatter_bands(int P, int T, int gx, int expected_instances, int forced)
     const int nchunks = gsr_num_chunks(P), gy = T / gx;
     if (forced > 0) return forced < gy ? forced : (gy > 0 ? gy : 1);  // gsr_tuning.scatter_bands
     const double per_chunk = (double)(expected_instances > 0 ? expected_instances : 0) / nchunks;
-    const size_t budget = 160 * 1024 - 8192 - 1024;
     for (int nb = 1; nb <= 16 && nb <= gy; nb *= 2) {
-        const size_t tb = (size_t)((gy + nb - 1) / nb) * gx, fixed = gsr_align(tb * 12 + 8);
+        const size_t cap = gsr_scatter_lds((size_t)((gy + nb - 1) / nb) * gx).stage_cap;
         // (the AVERAGE share has to fit: a workgroup whose share does not takes the direct path on its own.  Measured at config 4,
         // 2M Gaussians @1920x1080, scatter launch: 1 band 203 us, 2: 185, 4: 125, 8: 172, 16: 269 -- every band walks all the
         // chunk's Gaussians again, so more bands than needed cost more than they save; config 2 with 2 forced bands: 34 -> 42 us)
-        if (budget > fixed + 4096 && per_chunk / nb <= (double)((budget - fixed) / 10)) return nb;
+        if (cap && per_chunk / nb <= (double)cap) return nb;
     }
     return 1;  // nothing fits (huge image): the plain form with its direct stores
 }
@@ -1107,53 +1010,63 @@ hipError_t gsr_launch_scatter(const GsrFrame& f, const GsrScatterPass& pass)
     uint32_t* const offsets = pass.inference ? nullptr : geom.offsets;  // gradient-slot numbering: only a backward reads it
     const int gy = gx > 0 ? T / gx : 0;
     const int nbands = gsr_scatter_bands(P, T, gx, expected_instances, pass.forced_bands);
-    GsrFusedScan fs = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    GsrFusedScan fs = {};
     if (pass.fused_tile_scan && T <= GSR_MAX_TILES_LDS)
-        fs = GsrFusedScan{ image.tile_count, image.ranges, image.info, image.tile_work, image.sorted_len, image.need_full, pass.fused_info_host,
-                           pass.occlusion_cut ? (const uint32_t*)image.occ_drop : (const uint32_t*)nullptr, image.tile_group };
+        fs = GsrFusedScan{ image.tile_count, image.tile_group, gsr_tile_scan_out(image, pass.fused_info_host, pass.occlusion_cut) };
+    auto launch = [&](auto kernel, int workgroups, size_t lds, size_t stage_cap, int nb) {
+        hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(GSR_HIST_THREADS), lds, stream, P, T, gx, nchunks, geom.rect, geom.tmask,
+                           geom.depthkey, image.table, geom.scan_sums, image.ranges, offsets, bin.seg_keys, (uint32_t)capacity,
+                           (uint32_t)stage_cap, fs, nb, gy);
+        return hipGetLastError();
+    };
     if (T > GSR_MAX_TILES_LDS) {
         hipLaunchKernelGGL(gsr_cursor_init_kernel, dim3((T + 255) / 256), dim3(256), 0, stream, T, image.ranges, image.table);
-        hipLaunchKernelGGL((gsr_scatter_kernel<true, false>), dim3(nchunks), dim3(GSR_HIST_THREADS), 0, stream, P, T, gx, nchunks,
-                           geom.rect, geom.tmask, geom.depthkey, image.table, geom.scan_sums, image.ranges, offsets,
-                           bin.seg_keys, (uint32_t)capacity, 0u, fs, 1, gy);
-        return hipGetLastError();
+        return launch(gsr_scatter_kernel<true, false>, nchunks, 0, 0, 1);
     }
     hipError_t e = gsr_allow_big_lds();
     if (e != hipSuccess) return e;
     // dynamic LDS: the three per-tile arrays of the workgroup's band of tile rows + the staging buffer (10 B per instance).  Plain
     // form: as much staging as the CU has left (a chunk with more instances takes the direct path inside the same launch).  Banded
     // form: 1.3 x the expected (chunk, band) share -- a smaller footprint lets two workgroups share a CU.
-    const size_t budget = 160 * 1024 - 8192 - 1024;  // static arrays of the kernel: ~4.3 KiB
     const size_t tb = (size_t)((gy + nbands - 1) / nbands) * gx;
-    const size_t fixed = gsr_align(tb * 12 + 8);
-    size_t stage_cap = budget > fixed + 4096 ? (budget - fixed) / 10 : 0;
+    const GsrScatterLds plan = gsr_scatter_lds(tb);
+    size_t stage_cap = plan.stage_cap;
     if (nbands > 1) {
         const size_t want = (size_t)(1.3 * (double)(expected_instances > 0 ? expected_instances : 0) / nchunks / nbands) + 256;
         if (want < stage_cap) stage_cap = want;
     }
     stage_cap &= ~(size_t)63;
-    const size_t lds = stage_cap ? fixed + stage_cap * 10 : tb * 4;
-    if (nbands > 1)
-        hipLaunchKernelGGL((gsr_scatter_kernel<false, true>), dim3(nchunks * nbands), dim3(GSR_HIST_THREADS), lds, stream, P, T, gx, nchunks,
-                           geom.rect, geom.tmask, geom.depthkey, image.table, geom.scan_sums, image.ranges, offsets,
-                           bin.seg_keys, (uint32_t)capacity, (uint32_t)stage_cap, fs, nbands, gy);
-    else
-        hipLaunchKernelGGL((gsr_scatter_kernel<false, false>), dim3(nchunks), dim3(GSR_HIST_THREADS), lds, stream, P, T, gx, nchunks,
-                           geom.rect, geom.tmask, geom.depthkey, image.table, geom.scan_sums, image.ranges, offsets,
-                           bin.seg_keys, (uint32_t)capacity, (uint32_t)stage_cap, fs, 1, gy);
-    return hipGetLastError();
+    const size_t lds = stage_cap ? plan.fixed + stage_cap * 10 : tb * 4;
+    if (nbands > 1) return launch(gsr_scatter_kernel<false, true>, nchunks * nbands, lds, stage_cap, nbands);
+    return launch(gsr_scatter_kernel<false, false>, nchunks, lds, stage_cap, 1);
 }
 
 // Full sort of the lists in (lo0, ...] by size class: (.., SMALL] and (SMALL, LARGE] in LDS, longer in global memory.
 // The network is a chain of ~30 LDS round trips + barriers per workgroup and runs at the speed occupancy allows, and
 // virtual padding is never stored: the dynamic LDS is sized for the longest list that exists (8.5 B per key), not for
 // the class limit -- 11 KiB instead of 34 KiB on the bench scene, twice the resident workgroups.
-static hipError_t gsr_launch_full_sorts(int T, int capacity, uint32_t lo0, uint32_t max_tile_count, const GsrImage& image,
-                                        const GsrBinning& bin_in, const uint32_t* only_flagged, uint32_t* sorted_len,
-                                        bool inference, hipStream_t stream, bool split_at_near_cap = false)
+static GsrBinning gsr_sort_binning(const GsrBinning& bin_in, bool inference)
 {
     GsrBinning bin = bin_in;
     if (inference) bin.slot_written = nullptr;  // the written-slot flags belong to the backward
+    return bin;
+}
+// One LDS sort launch over the lists in (lo, cap], the longest of which has `longest` keys: 256 threads up to 2048 keys, 1024 beyond.
+static void gsr_launch_sort_lds(int T, int capacity, uint32_t lo, uint32_t cap, uint32_t longest, const GsrImage& image, const GsrBinning& bin,
+                                const uint32_t* only_flagged, uint32_t* sorted_len, hipStream_t stream)
+{
+    const size_t lds = gsr_align((size_t)GSR_PAD(longest) * 8 + 8);
+    if (longest <= 2048u)
+        hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<256>, dim3(T), dim3(256), lds, stream, image.ranges, bin.seg_keys,
+                           bin.point_list, bin.slot_written, lo, cap, longest, (uint32_t)capacity, only_flagged, sorted_len);
+    else
+        hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<1024>, dim3(T), dim3(1024), lds, stream, image.ranges, bin.seg_keys,
+                           bin.point_list, bin.slot_written, lo, cap, longest, (uint32_t)capacity, only_flagged, sorted_len);
+}
+static hipError_t gsr_launch_full_sorts(int T, int capacity, uint32_t lo0, uint32_t max_tile_count, const GsrImage& image,
+                                        const GsrBinning& bin, const uint32_t* only_flagged, uint32_t* sorted_len,
+                                        hipStream_t stream, bool split_at_near_cap = false)
+{
     // split_at_near_cap (the partial sort's bet is off, api.hip gsr_partial_bet): the many lists up to GSR_NEAR_CAP keep their 256-thread
     // kernel and only the few longer ones take the 1024-thread one (one class for both gives every 400-entry list 1024 threads)
     const uint32_t caps[] = { split_at_near_cap ? (uint32_t)GSR_NEAR_CAP : 0u, (uint32_t)GSR_SORT_CAP_SMALL, (uint32_t)GSR_SORT_CAP_LARGE };
@@ -1164,14 +1077,7 @@ static hipError_t gsr_launch_full_sorts(int T, int capacity, uint32_t lo0, uint3
                 const hipError_t e = gsr_allow_big_lds();
                 if (e != hipSuccess) return e;
             }
-            const uint32_t longest = min(cap, max_tile_count);
-            const size_t lds = gsr_align((size_t)GSR_PAD(longest) * 8 + 8);
-            if (longest <= 2048u)
-                hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<256>, dim3(T), dim3(256), lds, stream, image.ranges, bin.seg_keys,
-                                   bin.point_list, bin.slot_written, lo, cap, longest, (uint32_t)capacity, only_flagged, sorted_len);
-            else
-                hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<1024>, dim3(T), dim3(1024), lds, stream, image.ranges, bin.seg_keys,
-                                   bin.point_list, bin.slot_written, lo, cap, longest, (uint32_t)capacity, only_flagged, sorted_len);
+            gsr_launch_sort_lds(T, capacity, lo, cap, min(cap, max_tile_count), image, bin, only_flagged, sorted_len, stream);
         }
         lo = max(lo, cap);
     }
@@ -1188,28 +1094,22 @@ hipError_t gsr_launch_tile_sort(const GsrFrame& f, int max_tile_count, int parti
     const int T = f.T, capacity = f.capacity;
     const GsrImage& image = f.image;
     hipStream_t stream = f.stream;
-    GsrBinning bin = f.bin;
-    if (inference) bin.slot_written = nullptr;
+    const GsrBinning bin = gsr_sort_binning(f.bin, inference);
     // max_tile_count < 0: not known -> run every variant, blocks exit on mismatch.  speculative: max_tile_count is the
     // caller's guess (it sizes the LDS; the host checks it against the truth afterwards)
     if (capacity <= 0) return hipSuccess;
     const uint32_t mx = max_tile_count < 0 ? 0x7fffffffu : (uint32_t)max_tile_count;
-    if (partial != 1) return gsr_launch_full_sorts(T, capacity, 0u, mx, image, bin, nullptr, nullptr, inference, stream, partial == 2 && mx > GSR_NEAR_CAP);
+    if (partial != 1) return gsr_launch_full_sorts(T, capacity, 0u, mx, image, bin, nullptr, nullptr, stream, partial == 2 && mx > GSR_NEAR_CAP);
     // lists up to GSR_NEAR_CAP: full sort in LDS; longer ones: sorted prefix only (gsr_tile_sort_near_kernel)
     // (a guess below the cap that turns out too small fails the host's check anyway and stage 2 is redone)
     // (round 4 measured the alternative for frames whose longest list is in (2048, 4096] -- complete sorts, 256-thread kernel for the
     // lists up to 2048 + 1024-thread kernel for the longer ones: config 4 108 -> 122 us, large-splat frame after the occlusion
     // cut-off 133 -> 239 us: the prefix-sort kernel is not the slower one, the cost follows the number of keys)
-    if (mx > GSR_NEAR_CAP) {  // long lists exist: one launch does both classes (fixed 21 KiB of LDS)
+    if (mx > GSR_NEAR_CAP)  // long lists exist: one launch does both classes (fixed 21 KiB of LDS)
         hipLaunchKernelGGL(gsr_tile_sort_near_kernel, dim3(T), dim3(256), 0, stream, image.ranges, bin.seg_keys, bin.point_list,
                            bin.slot_written, image.sorted_len, (uint32_t)capacity);
-    } else {  // short lists only: LDS sized for the longest one (twice the resident workgroups on the bench scene)
-        const uint32_t longest = min((uint32_t)GSR_NEAR_CAP, mx);
-        const size_t lds = gsr_align((size_t)GSR_PAD(longest) * 8 + 8);
-        hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<256>, dim3(T), dim3(256), lds, stream, image.ranges, bin.seg_keys, bin.point_list,
-                           bin.slot_written, 0u, (uint32_t)GSR_NEAR_CAP, longest, (uint32_t)capacity, (const uint32_t*)nullptr,
-                           (uint32_t*)nullptr);
-    }
+    else  // short lists only: LDS sized for the longest one (twice the resident workgroups on the bench scene)
+        gsr_launch_sort_lds(T, capacity, 0u, (uint32_t)GSR_NEAR_CAP, min((uint32_t)GSR_NEAR_CAP, mx), image, bin, nullptr, nullptr, stream);
     return hipGetLastError();
 }
 
@@ -1217,6 +1117,6 @@ hipError_t gsr_launch_tile_sort(const GsrFrame& f, int max_tile_count, int parti
 hipError_t gsr_launch_sort_fixup(const GsrFrame& f, int max_tile_count, bool inference)
 {
     if (f.capacity <= 0 || max_tile_count <= GSR_NEAR_CAP) return hipSuccess;
-    return gsr_launch_full_sorts(f.T, f.capacity, (uint32_t)GSR_NEAR_CAP, (uint32_t)max_tile_count, f.image, f.bin, f.image.need_full,
-                                 f.image.sorted_len, inference, f.stream);
+    return gsr_launch_full_sorts(f.T, f.capacity, (uint32_t)GSR_NEAR_CAP, (uint32_t)max_tile_count, f.image, gsr_sort_binning(f.bin, inference),
+                                 f.image.need_full, f.image.sorted_len, f.stream);
 }

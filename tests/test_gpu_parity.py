@@ -795,6 +795,58 @@ def test_banded_scatter_gives_the_same_lists(bands):
         set_tuning()
 
 
+def _tile_scan_words(s, one_call, bands, tile_cull=False, occlusion_cut=False):
+    """One forward in the two-stage form (gsr_tile_scan_kernel writes the frame's tile-scan words) or the one-call form (workgroup 0
+    of the scatter does): the binning state and the words both forms must agree on."""
+    from gscream_amd import rasterizer as RZ
+    set_tuning(tile_cull=tile_cull, scatter_bands=bands, speculative=one_call, occlusion_cut=occlusion_cut)   # (clears the capacity hint)
+    for _rep in range(2 if one_call else 1):   # the second speculative call has a hint: the one-call form
+        got = Hh.hip_run(s, keep_state=True)
+    assert bool(RZ._last_stage1["speculative"]) == one_call
+    img = _layout.image_views(got["img"], s["means3D"].shape[0], s["W"], s["H"])
+    words = dict(num_rendered=got["num_rendered"], max_tile_count=RZ._last_stage1["max_tile_count"], num_occluded=RZ._last_stage1["num_occluded"])
+    words.update({k: img[k].cpu().numpy().copy() for k in ("ranges", "sorted_len", "need_full")})
+    return got, words
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,tiles", [(640, 480, 1200), (1296, 1040, 5265), (2064, 1600, 12900)])
+def test_both_tile_scans_write_the_same_words(W, H, tiles):
+    """The tile-scan words of a frame -- ranges, sorted_len, need_full, R, the longest list, the occluded count -- have two producers:
+    gsr_tile_scan_kernel<PER> (two-stage forward) and workgroup 0 of the scatter (one-call forward).  Both must match the oracle and
+    each other at every PER class of the kernel: 1200 tiles = two per thread (class 4), 81 x 65 = 5265 (class 12; the odd row width
+    keeps band edges off the 64-tile group edges the banded scatter starts its scan from), 129 x 100 = 12900 (class 36) -- with the
+    plain and the banded scatter.  These runs have tile culling off (the oracle's lists).  The occlusion part needs it ON: the library
+    switches the cut-off off when tile culling is disabled (api.hip gsr_occlusion), so with it off there is no dropped count to sum."""
+    assert ((W + 15) // 16) * ((H + 15) // 16) == tiles
+    s = S.scene_config1(seed=78, P=3000, W=W, H=H)
+    s["scales"] = (s["scales"] * np.float32(0.5)).astype(np.float32)   # spread over the frame, splats of several tiles
+    st = Hh.oracle_forward(s, nthreads=NT)
+    counts = (st["ranges"][:, 1] - st["ranges"][:, 0]).astype(np.int64)
+    try:
+        for bands in (0, 3):
+            forms = {}
+            for one_call in (False, True):
+                got, forms[one_call] = _tile_scan_words(s, one_call, bands)
+                assert got["num_rendered"] == st["num_rendered"]
+                _check_binning(s, got, st["point_list"], counts)
+            assert forms[False]["max_tile_count"] == int(counts.max())
+            for k, v in forms[False].items():
+                assert np.array_equal(v, forms[True][k]), (bands, k)
+        if tiles == 1200:   # + the sum of the occlusion cut-off's dropped instances (it needs the tile culling): big opaque splats among small ones
+            s["scales"][:500] *= np.float32(10.0)
+            s["opacities"][:500] = np.float32(0.9)
+            for bands in (0, 3):
+                off = _tile_scan_words(s, False, bands, tile_cull=True)[1]
+                forms = {one_call: _tile_scan_words(s, one_call, bands, tile_cull=True, occlusion_cut=True)[1] for one_call in (False, True)}
+                for k, v in forms[False].items():
+                    assert np.array_equal(v, forms[True][k]), (bands, k)
+                assert off["num_occluded"] == 0 and forms[True]["num_occluded"] > 0
+                assert forms[True]["num_rendered"] + forms[True]["num_occluded"] == off["num_rendered"]
+    finally:
+        set_tuning()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["stack_of_big_splats", "mixed", "bench_like", "walks_into_the_second_tier"])
 def test_occlusion_cutoff_changes_no_output_bit(case):
