@@ -15,16 +15,10 @@ CKPT_PLANES = SEG_MAX * 6
 SEG2_ENDS = tuple(SEG1 + T2_LEN * (j + 1) for j in range(T2_N)) + tuple(SEG1 + T2_LEN * T2_N + SEG3_LEN * (j + 1) for j in range(128))
 
 
-def seg2_len(n, L):
-    """The unit of the boundaries behind the first tier = the launch's segment length L (64 up to 4096 tiles, 128 beyond),
-    whatever the list length n."""
-    return L
-
-
-def ckpt_pos(k, L, unit):
-    """gsr_ckpt_pos: list position of checkpoint k = 0 .. SEG_MAX-2 (fixed positions: they do not depend on the list).
-    `unit` is always L."""
-    return (k + 1) * L if k < SEG1 else unit * SEG2_ENDS[k - SEG1]
+def ckpt_pos(k, L):
+    """gsr_ckpt_pos: list position of checkpoint k = 0 .. SEG_MAX-2 in the launch's segment length L (64 up to 4096 tiles, 128
+    beyond).  Fixed positions: they do not depend on the list."""
+    return L * (k + 1 if k < SEG1 else SEG2_ENDS[k - SEG1])
 
 
 def _align(x):

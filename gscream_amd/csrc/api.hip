@@ -412,9 +412,6 @@ extern "C" int gsr_forward_stage1(int P, int D, int M, int W, int H, const float
     return gsr_publish_stage1(state->host, result_host);
 }
 
-// where a forward renders to
-struct GsrTargets { const float* background; float* color; float* depth; float* feature; };
-
 // After a forward over partially sorted lists (binning.hip): tiles whose pixels were still blending at the end of their
 // sorted prefix get a full sort and are blended again.  Nothing happens on the GPU beyond a few empty launches when no
 // tile asked for it; not enqueued at all when no list was long enough to be partially sorted.
@@ -433,7 +430,7 @@ static int gsr_enqueue_fixup(const GsrFrame& f, int max_tile_count, const GsrTar
     pass.ranoff_report = s->dev + GSR_PINNED_RANOFF;  // where a resumed quadrant reports the lost bet (gsr_partial_bet)
     pass.serial = s->fwd_serial;
     GSR_STAGE(GSR_STAGE_BLEND_FWD, f.stream, f.debug,
-              gsr_launch_blend_forward(f, to.background, to.color, to.depth, to.feature, max_tile_count, pass), "forward blend (fix-up)");
+              gsr_launch_blend_forward(f, to, max_tile_count, pass), "forward blend (fix-up)");
     return GSR_OK;
 }
 
@@ -462,7 +459,7 @@ static int gsr_enqueue_stage2(const GsrFrame& f, hipEvent_t scattered, int longe
     pass.walk_depths_valid = walk.valid;
     pass.already_ordered = ordered;
     GSR_STAGE(GSR_STAGE_BLEND_FWD, f.stream, f.debug,
-              gsr_launch_blend_forward(f, to.background, to.color, to.depth, to.feature, longest, pass), "forward blend");
+              gsr_launch_blend_forward(f, to, longest, pass), "forward blend");
     // longest list known (exact form): the fix-up can follow at once; the speculative form enqueues it after the read-back
     if (!speculative && sort_mode == 1 && longest >= 0) return gsr_enqueue_fixup(f, longest, to, scatter.inference, walk);
     return GSR_OK;

@@ -144,14 +144,14 @@ __device__ __forceinline__ void gsr_fwd_order_block(int x, int T, int xt, const 
 #define GSR_SEG2 20      // segments behind the first tier: GSR_T2_N of the second tier + 13 of the third + the rest
 #define GSR_SEG_MAX (GSR_SEG1 + GSR_SEG2)   // segments per tile = checkpoint slots (GSR_SEG_MAX - 1 checkpoints + the "last" slot)
 #define GSR_CKPT_PLANES (GSR_SEG_MAX * 6)
-// list position of checkpoint k (k = 0 .. GSR_SEG_MAX-2) = end of segment k = start of segment k + 1.  `unit`, the unit of the boundaries
-// behind tier 1, is the launch's segment length L at every call site, whatever the list length
-__host__ __device__ static inline int gsr_ckpt_pos(int k, int L, int unit)
+// list position of checkpoint k (k = 0 .. GSR_SEG_MAX-2) = end of segment k = start of segment k + 1, in the launch's segment length L
+// (whatever the list length)
+__host__ __device__ static inline int gsr_ckpt_pos(int k, int L)
 {
     static_assert(GSR_SEG2 > GSR_T2_N + 1, "tiers");
     return k < GSR_SEG1 ? (k + 1) * L
-         : k < GSR_SEG1 + GSR_T2_N ? (GSR_SEG1 + GSR_T2_LEN * (k - GSR_SEG1 + 1)) * unit
-         : (GSR_SEG1 + GSR_T2_LEN * GSR_T2_N + GSR_SEG3_LEN * (k - GSR_SEG1 - GSR_T2_N + 1)) * unit;
+         : k < GSR_SEG1 + GSR_T2_N ? (GSR_SEG1 + GSR_T2_LEN * (k - GSR_SEG1 + 1)) * L
+         : (GSR_SEG1 + GSR_T2_LEN * GSR_T2_N + GSR_SEG3_LEN * (k - GSR_SEG1 - GSR_T2_N + 1)) * L;
 }
 // segments a backward launch has to cover for lists of up to `longest` entries (< 0: unknown): the one that holds position longest - 1
 // and everything in front of it (the workgroups of segments no list reaches would only be dispatched to leave at once)
@@ -159,7 +159,7 @@ static inline int gsr_segments_for(int longest, int L)
 {
     if (longest < 0) return GSR_SEG_MAX;
     int k = 0;
-    while (k < GSR_SEG_MAX - 1 && gsr_ckpt_pos(k, L, L) < longest) k++;
+    while (k < GSR_SEG_MAX - 1 && gsr_ckpt_pos(k, L) < longest) k++;
     return k + 1;
 }
 // Segment length of a launch: small images have few tiles, so their lists are cut finer to get enough tasks for the
@@ -356,6 +356,8 @@ struct GsrScatterPass {
     bool inference;             // no backward will follow: no gradient-slot numbering
     bool occlusion_cut;
 };
+// where a forward renders to
+struct GsrTargets { const float* background; float* color; float* depth; float* feature; };
 // what one forward-blend launch is asked for
 struct GsrBlendPass {
     bool only_flagged;        // fix-up pass: only the tiles that ran off their sorted prefix (image.need_full)
@@ -374,8 +376,7 @@ int gsr_scatter_bands(int P, int T, int gx, int expected_instances, int forced);
 hipError_t gsr_launch_scatter(const GsrFrame& f, const GsrScatterPass& pass);
 hipError_t gsr_launch_tile_sort(const GsrFrame& f, int max_tile_count, int partial /* 0 complete, 1 prefix bet, 2 complete with the long lists apart */,
                                 bool speculative, bool inference);
-hipError_t gsr_launch_blend_forward(const GsrFrame& f, const float* bg, float* out_color, float* out_depth, float* out_feature,
-                                    int max_tile_count, const GsrBlendPass& pass);
+hipError_t gsr_launch_blend_forward(const GsrFrame& f, const GsrTargets& to, int max_tile_count, const GsrBlendPass& pass);
 hipError_t gsr_launch_sort_fixup(const GsrFrame& f, int max_tile_count, bool inference);
 hipError_t gsr_launch_blend_backward(const GsrFrame& f, const float* bg, const float* dL_dcolor, const float* dL_ddepth,
                                      const float* dL_dfeature, float* slots, uint8_t* slot_written, uint32_t* heavy_groups,

@@ -20,6 +20,15 @@ __device__ __forceinline__ unsigned long long gsr_wave_scan_add(unsigned long lo
     return v;
 }
 
+// maximum over the wave, in every lane (int or uint32_t)
+template <typename T>
+__device__ __forceinline__ T gsr_wave_max(T v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, (T)__shfl_xor((int)v, d, 64));
+    return v;
+}
+
 // Exclusive scan over a block of NT threads, in place, of C independent values per thread behind one barrier; the block's
 // totals go to totals[0..C) when given.  LOOP = true: the C * NT / 64 wave totals are read in a loop over the waves, not all at
 // once -- the caller's choice, for a kernel at its register budget (the binning's scatter, C = 4 and 1024 threads: 82 -> 110 VGPRs

@@ -911,18 +911,27 @@ def test_occlusion_cutoff_changes_no_output_bit(case):
         assert len(b) >= int(off["tile_work"][t]), f"tile {t}: the cut-off removed an instance the forward walks"
 
 
+def _faint_splats_scene():
+    """Scene, upstream gradients and oracle forward of a frame of faint splats: nothing saturates, every list is walked to its end.
+    Scene and gradients are the caller's own; the oracle's result is computed once and shared, read-only."""
+    s = S.scene_config1(seed=91, P=6000, W=64, H=48, lateral=0.35)
+    s["opacities"] = (s["opacities"] * 0.02 + 0.004).astype(np.float32)       # 0.005 .. 0.023: T stays near 1 over thousands of blends
+    s["scales"] = (s["scales"] * 2.0).astype(np.float32)
+    if not _faint_splats_oracle:
+        _faint_splats_oracle.append(Hh.oracle_forward(s))
+    return s, S.upstream_grads(91, s["W"], s["H"]), _faint_splats_oracle[0]
+
+
+_faint_splats_oracle = []
+
+
 def test_second_tier_of_depth_segments():
     """Round 5: lists longer than seven tier-1 segments are cut into GSR_SEG2 more segments at fixed list positions
     (gsr_common.h gsr_ckpt_pos) instead of leaving everything behind position 448 to ONE backward task.  A frame of
     faint splats -- nothing saturates, every list is walked to its end, like an initialised, untrained scene -- with lists well
     beyond 448 entries: images and gradients against the oracle, the checkpoints a pixel wrote sit where the two-tier rule puts them
     (the sums of the closed segments + the open one reproduce the image), and the backward stays bit-reproducible."""
-    from gscream_amd import _layout
-    s = S.scene_config1(seed=91, P=6000, W=64, H=48, lateral=0.35)
-    s["opacities"] = (s["opacities"] * 0.02 + 0.004).astype(np.float32)       # 0.005 .. 0.023: T stays near 1 over thousands of blends
-    s["scales"] = (s["scales"] * 2.0).astype(np.float32)
-    grads = S.upstream_grads(91, s["W"], s["H"])
-    st = Hh.oracle_forward(s)
+    s, grads, st = _faint_splats_scene()
     ref = Hh.oracle_backward(s, st, grads)
     ll = (st["ranges"][:, 1].astype(np.int64) - st["ranges"][:, 0])
     assert ll.max() > 7 * 64 + 8 * 64, f"the scene must reach the second tier (longest list {ll.max()})"
@@ -949,11 +958,10 @@ def test_second_tier_of_depth_segments():
         for x in range(0, W, 7):
             t = (y // 16) * gx + x // 16
             n = int(ranges[t, 1] - ranges[t, 0])
-            L2 = _layout.seg2_len(n, 64)
             # a pixel passes checkpoint k iff its QUADRANT's walk reached that list position: at least every checkpoint in front
             # of its own last contributor
-            must = sum(1 for k in range(SM - 1) if _layout.ckpt_pos(k, 64, L2) < ncon[y, x])
-            assert npass[y, x] >= must, (x, y, n, L2, int(ncon[y, x]), int(npass[y, x]))
+            must = sum(1 for k in range(SM - 1) if _layout.ckpt_pos(k, 64) < ncon[y, x])
+            assert npass[y, x] >= must, (x, y, n, int(ncon[y, x]), int(npass[y, x]))
     k = torch.arange(SM - 1, device="cuda")[:, None]
     live = k < a[SM - 1, :, 0].view(torch.int32).long()[None, :]
     sums = torch.where(live[:, :, None], a[:SM - 1, :, 1:], torch.zeros_like(a[:SM - 1, :, 1:])).sum(0) + a[SM - 1, :, 1:]
@@ -961,6 +969,68 @@ def test_second_tier_of_depth_segments():
     bg = torch.from_numpy(s["bg"]).cuda()
     img = sums.t().reshape(3, H, W) + fT.reshape(1, H, W) * bg[:, None, None]
     assert (img.cpu().numpy() - keep["out_color"]).max() < 1e-5
+
+
+def _guard_band_pairs(s, st, width):
+    """(pixel x, pixel y, Gaussian) of the blending pairs whose reference alpha o exp(power) lies within `width` / 255 of 1 / 255
+    (float64 on the oracle's means2D / conic_opacity, over the oracle's own tile lists) + the number of blending pairs."""
+    W, H = s["W"], s["H"]
+    gx = (W + 15) // 16
+    m2, co = st["means2D"].astype(np.float64), st["conic_opacity"].astype(np.float64)
+    pairs, blending = [], 0
+    for t, (a, b) in enumerate(st["ranges"].astype(np.int64)):
+        g = st["point_list"][a:b].astype(np.int64)
+        ys, xs = np.meshgrid(np.arange((t // gx) * 16, min((t // gx) * 16 + 16, H)), np.arange((t % gx) * 16, min((t % gx) * 16 + 16, W)), indexing="ij")
+        xs, ys = xs.reshape(-1), ys.reshape(-1)
+        dx, dy = m2[g, 0][:, None] - xs[None, :], m2[g, 1][:, None] - ys[None, :]
+        power = -0.5 * (co[g, 0][:, None] * dx * dx + co[g, 2][:, None] * dy * dy) - co[g, 1][:, None] * dx * dy
+        alpha = co[g, 3][:, None] * np.exp(np.minimum(power, 0.0))
+        blending += int(((power <= 0) & (alpha >= 1.0 / 255.0)).sum())
+        gi, pi = np.nonzero((power <= 0) & (np.abs(alpha - 1.0 / 255.0) < width / 255.0))
+        pairs += [(int(xs[p_]), int(ys[p_]), int(g[g_])) for g_, p_ in zip(gi, pi)]
+    return pairs, blending
+
+
+def test_guard_band_entries_are_flagged_and_settled_alike():
+    """The alpha = 1/255 guard band (blend.hip GSR_BAND, gsr_band_settle).  On the frame of faint splats nothing saturates, so every
+    binned pair is walked: every (pixel, Gaussian) pair whose reference alpha lies in the inner half of the band -- 1.5e-5 relative, far
+    more than the few 1e-7 by which the fast alpha differs -- must leave bit 31 set on that Gaussian's entry of the pixel's tile list
+    (lists sorted once: partial_sort off, so the flags survive), and the backward, which settles the flagged entries only, must give
+    the same bits as the one that settles every entry: flag-driven check = check everything.  The backward settles every entry of a
+    tile whose list was sorted a second time (need_full: the flags of its first pass are lost), i.e. of a list beyond 2048 entries that
+    lost the partial sort's bet.  With the default tuning tile culling may leave no such list on this scene, so the comparison is made
+    a second time on the oracle's lists (tile_cull off), where a tile that holds an in-band pair must have been sorted twice."""
+    s, grads, st = _faint_splats_scene()
+    pairs, blending = _guard_band_pairs(s, st, 1.5e-5)
+    print(f"guard band: {len(pairs)} pairs in its inner half of {blending} blending pairs")
+    assert len(pairs) >= 4, "the scene must put some pairs inside the guard band"
+    P, W, H = s["means3D"].shape[0], s["W"], s["H"]
+    tile_of = lambda x, y: (y // 16) * ((W + 15) // 16) + x // 16
+    try:
+        for cull in (True, False):
+            set_tuning(tile_cull=cull, partial_sort=False)
+            keep = Hh.hip_run(s, keep_state=True)
+            rng = _layout.image_views(keep["img"], P, W, H)["ranges"].cpu().numpy().astype(np.int64)
+            bv = _layout.binning_views(keep["binning"], keep["num_rendered"], keep["binning_capacity"])
+            pl, flag = bv["point_list"].cpu().numpy().astype(np.int64), bv["band_flag"].cpu().numpy()
+            for x, y, g in pairs:
+                a, b = rng[tile_of(x, y)]
+                at = np.flatnonzero(pl[a:b] == g)
+                assert at.size == 1, f"Gaussian {g} must be in the list of pixel ({x}, {y})'s tile"
+                assert flag[a + at[0]], f"pixel ({x}, {y}) met Gaussian {g} inside the guard band: its list entry must carry bit 31"
+            flagged_only = Hh.hip_run(s, grads)
+            set_tuning(tile_cull=cull)                           # (set_tuning resets the partial sort's feedback: this forward bets)
+            need_full = _layout.image_views(Hh.hip_run(s, keep_state=True)["img"], P, W, H)["need_full"].cpu().numpy().astype(bool)
+            print(f"tile_cull={cull}: {int(need_full.sum())} tiles sorted twice, in-band pairs in {sum(bool(need_full[tile_of(x, y)]) for x, y, _ in pairs)} of them")
+            if not cull:
+                assert any(need_full[tile_of(x, y)] for x, y, _ in pairs), "a tile with an in-band pair must lose the partial sort's bet"
+            set_tuning(tile_cull=cull)
+            every_entry = Hh.hip_run(s, grads)
+            for k in Hh.GRAD_KEYS:
+                if k in flagged_only:
+                    assert np.array_equal(flagged_only[k], every_entry[k]), f"{k} (tile_cull={cull}): settling the flagged entries = settling every entry"
+    finally:
+        set_tuning()
 
 
 def test_init_state_frame_against_the_oracle():

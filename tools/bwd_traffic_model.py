@@ -48,7 +48,7 @@ def main():
     n_list = rng[:, 1] - rng[:, 0]
     work = iv["tile_work"].long().cpu().numpy()
     nproc = np.minimum(n_list, work)
-    pos = np.array([_layout.ckpt_pos(k, L, L) for k in range(S - 1)], np.int64)
+    pos = np.array([_layout.ckpt_pos(k, L) for k in range(S - 1)], np.int64)
     ncon = (iv["n_contrib"].long() & 0x3fffffff).cpu().numpy().reshape(H, W)
     N, Np = W * H, (W * H + 3) & ~3
     npass = iv["ckpt"][S - 1, :4 * Np].reshape(Np, 4)[:N, 0].contiguous().view(torch.int32).long().cpu().numpy().reshape(H, W)
