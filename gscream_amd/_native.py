@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "gsr_anchor_grow_workspace_bytes", "gsr_anchor_grow_keys", "gsr_anchor_grow_emit", "gsr_scatter_max",
     "gsr_crossattn_workspace_bytes", "gsr_crossattn_forward", "gsr_crossattn_backward",
     "gsr_anchor_sample_workspace_bytes", "gsr_anchor_sample",
+    "gsr_anchor_adjust_workspace_bytes", "gsr_anchor_adjust_offsets", "gsr_anchor_adjust_plan", "gsr_anchor_adjust_gather",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -40,6 +41,15 @@ class Tuning(ctypes.Structure):
                 ("disable_partial_sort", ctypes.c_int32), ("inference", ctypes.c_int32), ("scatter_bands", ctypes.c_int32),
                 ("occlusion_cut", ctypes.c_int32), ("heavy_groups", ctypes.c_int32), ("walk_depths_valid", ctypes.c_int32),
                 ("walk_depths", ctypes.c_uint64)]
+
+
+class AdjustCopy(ctypes.Structure):
+    """gsr_adjust_copy: one tensor of gsr_anchor_adjust_gather's table (device pointers, floats per anchor row, ADJUST_* mode)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("width", ctypes.c_int32), ("mode", ctypes.c_int32)]
+
+
+ADJUST_MAX_COPIES = 32
+ADJUST_COPY, ADJUST_CLAMP_TAIL, ADJUST_OFFSET_STAT, ADJUST_ANCHOR_STAT = range(4)
 
 
 class Profile(ctypes.Structure):
@@ -159,6 +169,14 @@ def load():
     lib.gsr_anchor_sample_workspace_bytes.argtypes = [_c_int, _c_int]
     lib.gsr_anchor_sample.restype = _c_int
     lib.gsr_anchor_sample.argtypes = [_c_int] * 3 + [_vp] * 4 + [_c_int] * 5 + [ctypes.c_uint64] + [_vp] * 7
+    lib.gsr_anchor_adjust_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_anchor_adjust_workspace_bytes.argtypes = [_c_int]
+    lib.gsr_anchor_adjust_offsets.restype = _c_int
+    lib.gsr_anchor_adjust_offsets.argtypes = [_c_int, _vp, _vp, _c_float, _vp, _vp, _vp]
+    lib.gsr_anchor_adjust_plan.restype = _c_int
+    lib.gsr_anchor_adjust_plan.argtypes = [_c_int, _vp, _vp, _vp, _c_float, _c_float] + [_vp] * 5
+    lib.gsr_anchor_adjust_gather.restype = _c_int
+    lib.gsr_anchor_adjust_gather.argtypes = [_c_int] * 3 + [ctypes.POINTER(AdjustCopy), _vp, _vp, _c_int, _vp, _vp]
     _lib = lib
     return lib
 

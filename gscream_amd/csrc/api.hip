@@ -971,3 +971,59 @@ extern "C" int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, co
             "anchor sample");
     return GSR_OK;
 }
+
+// ---- anchor pruning (anchor_adjust.hip) ----
+extern "C" size_t gsr_anchor_adjust_workspace_bytes(int N)
+{
+    if (N < 0 || N > 0x7fffff00) return 0;
+    return gaa_workspace_bytes(N);
+}
+
+extern "C" int gsr_anchor_adjust_offsets(int L0, const float* offset_gradient_accum, const float* offset_denom, float denom_threshold,
+                                         float* grads_norm, uint8_t* offset_mask, void* stream)
+{
+    if (L0 < 0 || L0 > 0x7fffff00) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust offsets: bad size L0=%d", L0);
+    if (L0 > 0 && (!offset_gradient_accum || !offset_denom || !grads_norm || !offset_mask))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust offsets: a required pointer is NULL");
+    GSR_HIP(gaa_launch_offsets(L0, offset_gradient_accum, offset_denom, denom_threshold, grads_norm, offset_mask, (hipStream_t)stream),
+            "anchor adjust offsets");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_adjust_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask,
+                                      float min_opacity, float demon_threshold, void* workspace, int32_t* keep_rows, uint8_t* reset,
+                                      int32_t* info, void* stream)
+{
+    if (N < 0 || N > 0x7fffff00) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust plan: bad size N=%d", N);
+    if (!info || (N > 0 && (!workspace || !keep_rows || !reset || (!prune_mask && (!opacity_accum || !anchor_demon)))))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust plan: a required pointer is NULL");
+    GSR_HIP(gaa_launch_plan(N, opacity_accum, anchor_demon, prune_mask, min_opacity, demon_threshold, workspace, keep_rows, reset, info,
+                            (hipStream_t)stream),
+            "anchor adjust plan");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_adjust_gather(int N, int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows,
+                                        const uint8_t* offset_mask, int L0, const uint8_t* reset, void* stream)
+{
+    if (N < 0 || n_keep < 0 || n_keep > N || n_copies < 0 || n_copies > GSR_ADJUST_MAX_COPIES || L0 < 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: bad sizes N=%d n_keep=%d n_copies=%d L0=%d", N, n_keep, n_copies, L0);
+    if (n_keep == 0 || n_copies == 0) return GSR_OK;
+    if (!copies || !keep_rows) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copies / keep_rows is NULL");
+    for (int c = 0; c < n_copies; c++) {
+        const gsr_adjust_copy& d = copies[c];
+        if (d.width < 1 || (long long)N * d.width > 0x7fffffffLL || d.mode < GSR_ADJUST_COPY || d.mode > GSR_ADJUST_ANCHOR_STAT)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d has width %d, mode %d (need 1 <= width, N*width < 2^31)", c,
+                            d.width, d.mode);
+        if (!d.dst || (!d.src && !(d.mode == GSR_ADJUST_OFFSET_STAT && L0 == 0)))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d has a NULL pointer", c);
+        if (d.mode == GSR_ADJUST_OFFSET_STAT && L0 > 0 && !offset_mask)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d is OFFSET_STAT but offset_mask is NULL", c);
+        if (d.mode == GSR_ADJUST_OFFSET_STAT && (long long)L0 > (long long)N * d.width)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: L0=%d exceeds N*K=%lld", L0, (long long)N * d.width);
+        if (d.mode == GSR_ADJUST_ANCHOR_STAT && (d.width != 1 || !reset))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d is ANCHOR_STAT: width must be 1 and reset given", c);
+    }
+    GSR_HIP(gaa_launch_gather(n_keep, n_copies, copies, keep_rows, offset_mask, L0, reset, (hipStream_t)stream), "anchor adjust gather");
+    return GSR_OK;
+}

@@ -458,3 +458,12 @@ size_t gas_workspace_bytes(int N, int max_pairs);
 hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask, int min_y,
                       int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace, uint8_t* src_mask, uint8_t* dst_mask,
                       int64_t* src_rows, int64_t* dst_rows, int32_t* info, hipStream_t stream);
+
+// ---- anchor_adjust.hip (GaussianModel.adjust_anchor / prune_anchor: offset statistics, prune plan, one table-driven row gather) ----
+size_t gaa_workspace_bytes(int N);
+hipError_t gaa_launch_offsets(int L0, const float* accum, const float* denom, float thr_half, float* grads_norm, uint8_t* offset_mask,
+                              hipStream_t stream);
+hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask, float min_opacity, float thr,
+                           void* workspace, int32_t* keep_rows, uint8_t* reset, int32_t* info, hipStream_t stream);
+hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows, const uint8_t* offset_mask,
+                             int L0, const uint8_t* reset, hipStream_t stream);

@@ -375,6 +375,51 @@ int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, const float* 
                       int32_t* info /* [8]: n_sampled, n_fg, n_bg, min_num, ok, 0, 0, 0 */, void* stream);
 
 /*
+ * Anchor pruning: GaussianModel.adjust_anchor around its anchor_growing call, with prune_anchor / _prune_anchor_optimizer
+ * (scene/gaussian_model.py:914-973, :762-805).  fp32 / integer, no atomics: repeated calls give identical bits.  Python scalars
+ * arrive rounded to fp32, which is how torch compares / multiplies a float tensor with them.
+ *   gsr_anchor_adjust_offsets (:916-919), over the L0 = N0*K offset rows that exist BEFORE growing:
+ *     g = offset_gradient_accum / offset_denom (IEEE fp32 division), NaN -> 0, grads_norm[L0] = |g|,
+ *     offset_mask[L0] (one byte, 0 / 1) = offset_denom > denom_threshold  ((float)(check_interval*success_threshold*0.5)).
+ *   gsr_anchor_adjust_plan (:937-939), over the N anchors that exist AFTER growing (opacity_accum[N], anchor_demon[N]):
+ *     reset = anchor_demon > demon_threshold  ((float)(check_interval*success_threshold));
+ *     prune = reset and opacity_accum < anchor_demon * min_opacity  (one fp32 product).
+ *     With prune_mask[N] (one byte per anchor) given, prune is that mask and reset is all zero (the standalone prune_anchor;
+ *     opacity_accum / anchor_demon may then be NULL).
+ *     Writes keep_rows[0:n_keep] (int32, the kept anchors in ASCENDING order; buffer of N entries, the rest untouched), reset[N]
+ *     (one byte, 0 / 1) and info[4] = {n_keep, n_prune, n_reset, 0} (int32, on the device).  A fixed number of launches, no
+ *     read-back.  N == 0 is valid.  workspace: gsr_anchor_adjust_workspace_bytes(N).
+ *   gsr_anchor_adjust_gather: ONE launch moves the kept rows of up to GSR_ADJUST_MAX_COPIES tensors.  `copies` is a HOST array; it
+ *     travels in the kernel arguments (no host-to-device copy).  Copy c treats dst as a flat stream of n_keep * width floats:
+ *     element e -> row = e / width, col = e % width, a = keep_rows[row], s = a * width + col, and by mode
+ *       GSR_ADJUST_COPY         dst[e] = src[s]                                   bit for bit (NaN, -0.0)
+ *       GSR_ADJUST_CLAMP_TAIL   col >= 3: v > 0.05f ? 0.05f : v (NaN stays), else COPY     the `scaling` parameter (:776-780), not its moments
+ *       GSR_ADJUST_OFFSET_STAT  width K: (s < L0 && !offset_mask[s]) ? src[s] : +0.0f      the resets :924/:930, the zero padding
+ *                               :925-934 and the gather :942-950 of offset_denom / offset_gradient_accum; src has L0 entries
+ *                               and is never read beyond them
+ *       GSR_ADJUST_ANCHOR_STAT  width 1: reset[a] ? +0.0f : src[s]                         :953-956 with :958-968
+ *     COPY / CLAMP_TAIL rows move in units of 16 or 8 bytes where the width is a multiple of 4 or 2 floats and both pointers are
+ *     aligned to the unit (checked per copy on the host), else float by float; any alignment of 4 is accepted.
+ *     N is the row count of the sources (keep_rows[] < N; N * width < 2^31 for every copy), n_keep the host's copy of info[0].
+ */
+#define GSR_ADJUST_MAX_COPIES 32
+enum { GSR_ADJUST_COPY = 0, GSR_ADJUST_CLAMP_TAIL = 1, GSR_ADJUST_OFFSET_STAT = 2, GSR_ADJUST_ANCHOR_STAT = 3 };
+typedef struct gsr_adjust_copy {
+    const float* src;
+    float* dst;
+    int32_t width; /* floats per anchor row */
+    int32_t mode;  /* GSR_ADJUST_* */
+} gsr_adjust_copy;
+size_t gsr_anchor_adjust_workspace_bytes(int N);
+int gsr_anchor_adjust_offsets(int L0, const float* offset_gradient_accum, const float* offset_denom, float denom_threshold,
+                              float* grads_norm, uint8_t* offset_mask, void* stream);
+int gsr_anchor_adjust_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask /* or NULL */,
+                           float min_opacity, float demon_threshold, void* workspace, int32_t* keep_rows /* [N] */,
+                           uint8_t* reset /* [N] */, int32_t* info /* [4]: n_keep, n_prune, n_reset, 0 */, void* stream);
+int gsr_anchor_adjust_gather(int N, int n_keep, int n_copies, const gsr_adjust_copy* copies /* host */, const int32_t* keep_rows,
+                             const uint8_t* offset_mask /* [L0] */, int L0, const uint8_t* reset /* [N] */, void* stream);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
