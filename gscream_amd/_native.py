@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "gsr_crossattn_workspace_bytes", "gsr_crossattn_forward", "gsr_crossattn_backward",
     "gsr_anchor_sample_workspace_bytes", "gsr_anchor_sample",
     "gsr_anchor_adjust_workspace_bytes", "gsr_anchor_adjust_offsets", "gsr_anchor_adjust_plan", "gsr_anchor_adjust_gather",
+    "gsr_adam_step",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -50,6 +51,16 @@ class AdjustCopy(ctypes.Structure):
 
 ADJUST_MAX_COPIES = 32
 ADJUST_COPY, ADJUST_CLAMP_TAIL, ADJUST_OFFSET_STAT, ADJUST_ANCHOR_STAT = range(4)
+
+
+class AdamTensor(ctypes.Structure):
+    """gsr_adam_tensor: one tensor of gsr_adam_step's table (device pointers, element count, the seven fp32 scalars of its update)."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int32),
+                ("b1", ctypes.c_float), ("c1", ctypes.c_float), ("b2", ctypes.c_float), ("c2", ctypes.c_float), ("s2", ctypes.c_float),
+                ("e", ctypes.c_float), ("a", ctypes.c_float)]
+
+
+ADAM_MAX_TENSORS = 32
 
 
 class Profile(ctypes.Structure):
@@ -177,6 +188,8 @@ def load():
     lib.gsr_anchor_adjust_plan.argtypes = [_c_int, _vp, _vp, _vp, _c_float, _c_float] + [_vp] * 5
     lib.gsr_anchor_adjust_gather.restype = _c_int
     lib.gsr_anchor_adjust_gather.argtypes = [_c_int] * 3 + [ctypes.POINTER(AdjustCopy), _vp, _vp, _c_int, _vp, _vp]
+    lib.gsr_adam_step.restype = _c_int
+    lib.gsr_adam_step.argtypes = [_c_int, ctypes.POINTER(AdamTensor), _vp]
     _lib = lib
     return lib
 

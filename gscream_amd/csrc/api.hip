@@ -1027,3 +1027,22 @@ extern "C" int gsr_anchor_adjust_gather(int N, int n_keep, int n_copies, const g
     GSR_HIP(gaa_launch_gather(n_keep, n_copies, copies, keep_rows, offset_mask, L0, reset, (hipStream_t)stream), "anchor adjust gather");
     return GSR_OK;
 }
+
+// ---- optimiser step (adam.hip) ----
+extern "C" int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, void* stream)
+{
+    if (n_tensors < 0 || n_tensors > GSR_ADAM_MAX_TENSORS)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: n_tensors=%d (need 0 .. %d)", n_tensors, GSR_ADAM_MAX_TENSORS);
+    if (n_tensors == 0) return GSR_OK;
+    if (!tensors) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensors is NULL");
+    for (int c = 0; c < n_tensors; c++) {
+        const gsr_adam_tensor& t = tensors[c];
+        if (t.n < 0 || t.n > 0x7fffff00)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a bad size n=%d (need 0 <= n <= 2^31 - 256)", c, t.n);
+        if (t.n > 0 && (!t.p || !t.g || !t.m || !t.v)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a NULL pointer", c);
+        if (t.n > 0 && (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a pointer that is not 4-byte aligned", c);
+    }
+    GSR_HIP(adam_launch(n_tensors, tensors, (hipStream_t)stream), "adam step");
+    return GSR_OK;
+}

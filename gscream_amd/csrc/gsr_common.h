@@ -467,3 +467,6 @@ hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* ancho
                            void* workspace, int32_t* keep_rows, uint8_t* reset, int32_t* info, hipStream_t stream);
 hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows, const uint8_t* offset_mask,
                              int L0, const uint8_t* reset, hipStream_t stream);
+
+// adam.hip: one launch for all tensors (validated by the caller; tensors with n == 0 are skipped)
+hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_t stream);

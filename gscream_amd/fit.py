@@ -140,17 +140,21 @@ def psnr(a, b):
     return float(-10.0 * torch.log10(torch.mean((a - b) ** 2).clamp_min(1e-12)))
 
 
-def fit(model, cams, gts, gdepths, iters, seed=0, lambda_dssim=0.2, depth_weight=1.0, bg=None, log_every=0):
+def fit(model, cams, gts, gdepths, iters, seed=0, lambda_dssim=0.2, depth_weight=1.0, bg=None, log_every=0, optimizer=None):
     """`iters` iterations of train.py's loop on the HIP rows.  Returns {"loss": [...], "psnr_first", "psnr_last", "ms_per_iteration"}
-    (PSNR of camera 0, rendered in eval mode before and after)."""
+    (PSNR of camera 0, rendered in eval mode before and after).  `optimizer`: a callable, parameter groups -> optimiser (e.g.
+    lambda groups: gscream_amd.adam.Adam(groups, lr=0.0, eps=1e-15)); None = torch's Adam as constructed below."""
     dev = gts.device
     bg = torch.zeros(3, device=dev) if bg is None else bg
     # (eps: scene/gaussian_model.py:392.  fused: one kernel per parameter group instead of eight foreach kernels -- the same update rule;
     # seven groups x eight launches were 0.5 ms of host time per iteration of a loop that is host-paced)
-    try:
-        opt = torch.optim.Adam(adam_groups(model), lr=0.0, eps=1e-15, fused=True)
-    except (RuntimeError, TypeError):
-        opt = torch.optim.Adam(adam_groups(model), lr=0.0, eps=1e-15)
+    if optimizer is not None:
+        opt = optimizer(adam_groups(model))
+    else:
+        try:
+            opt = torch.optim.Adam(adam_groups(model), lr=0.0, eps=1e-15, fused=True)
+        except (RuntimeError, TypeError):
+            opt = torch.optim.Adam(adam_groups(model), lr=0.0, eps=1e-15)
     rng = np.random.default_rng(seed)
     stack = []
     ones = torch.ones_like(gdepths[0])
@@ -192,9 +196,9 @@ def fit(model, cams, gts, gdepths, iters, seed=0, lambda_dssim=0.2, depth_weight
             "ms_per_iteration": t0.elapsed_time(t1) / max(iters, 1)}
 
 
-def scene_fitted(seed, W, H, iters=400, n_student=200_000, n_teacher=600_000, V=16, tanfovx=0.6, K=10, device="cuda", return_info=False):
+def scene_fitted(seed, W, H, iters=400, n_student=200_000, n_teacher=600_000, V=16, tanfovx=0.6, K=10, device="cuda", return_info=False, optimizer=None):
     """The rasterizer-level scene dict of the student's frame at the reference camera after `iters` optimiser steps (decoded in eval
-    mode, like scene_init_state), + what the run did."""
+    mode, like scene_init_state), + what the run did.  `optimizer`: as in fit()."""
     from . import neural_gaussians as NG
     ts = teacher_scene(seed + 100, n_teacher, W, H, tanfovx, device)
     centre = ts["means3D"].astype(np.float64).mean(0)
@@ -203,7 +207,7 @@ def scene_fitted(seed, W, H, iters=400, n_student=200_000, n_teacher=600_000, V=
     pts = SM.voxelize(S.surface_point_cloud(seed, n_student, tanfovx, H / W), 0.001)
     anchors = torch.from_numpy(pts).float().to(device)
     model = SM.Model.from_pcd(anchors, torch.clamp_min(KN.distCUDA2(anchors), 0.0000001), K=K, seed=seed).to(device)
-    info = fit(model, cams, gts, gdepths, iters, seed=seed, log_every=max(1, iters // 8))
+    info = fit(model, cams, gts, gdepths, iters, seed=seed, log_every=max(1, iters // 8), optimizer=optimizer)
     model.eval()
     with torch.no_grad():
         xyz, color, opacity, unc, scaling, rot = NG.generate_neural_gaussians(cams[0], model, None, is_training=False)

@@ -420,6 +420,32 @@ int gsr_anchor_adjust_gather(int N, int n_keep, int n_copies, const gsr_adjust_c
                              const uint8_t* offset_mask /* [L0] */, int L0, const uint8_t* reset /* [N] */, void* stream);
 
 /*
+ * The optimiser step: gaussians.optimizer.step() (train.py:611, :615), Adam without amsgrad / weight decay, for up to
+ * GSR_ADAM_MAX_TENSORS tensors of any parameter groups in ONE launch.  `tensors` is a HOST array; it travels in the kernel
+ * arguments (no host-to-device copy).  Per element, fp32, one rounding per operation (nothing contracts into an FMA), in the order of
+ * torch 1.12's mul_().add_(alpha=), mul_().addcmul_(value=), sqrt()/bias_correction2_sqrt .add_(eps), addcdiv_(value=):
+ *     m' = m*b1 + g*c1                 b1 = (float)beta1, c1 = (float)(1 - beta1)
+ *     v' = v*b2 + (c2*g)*g             b2 = (float)beta2, c2 = (float)(1 - beta2)
+ *     d  = sqrt(v') / s2 + e           s2 = (float)sqrt(1 - beta2^t), e = (float)eps
+ *     p' = p + (a*m') / d              a  = (float)(-(lr / (1 - beta1^t)))
+ * sqrt and both divisions are the correctly rounded ones; fp32 denormals are kept.  The caller computes each scalar in double from
+ * the group's lr, betas, eps and the parameter's own step count t (after its increment) and rounds it once to fp32, which is how
+ * torch passes Python scalars to its kernels.  p, m and v are updated in place; g is read only.  Tensors whose four pointers are all
+ * 16-byte aligned move in 16-byte units (the n % 4 floats behind them singly), others float by float; any alignment of 4 is accepted.
+ * No atomics: repeated calls give identical bits.  n_tensors == 0 and tensors with n == 0 (whose pointers may be NULL) do nothing.
+ */
+#define GSR_ADAM_MAX_TENSORS 32
+typedef struct gsr_adam_tensor {
+    float* p;       /* [n] parameter, in place */
+    const float* g; /* [n] gradient */
+    float* m;       /* [n] exp_avg, in place */
+    float* v;       /* [n] exp_avg_sq, in place */
+    int32_t n;      /* elements, 0 <= n < 2^31 */
+    float b1, c1, b2, c2, s2, e, a;
+} gsr_adam_tensor;
+int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors /* host */, void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
