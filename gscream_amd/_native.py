@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "gsr_anchor_sample_workspace_bytes", "gsr_anchor_sample",
     "gsr_anchor_adjust_workspace_bytes", "gsr_anchor_adjust_offsets", "gsr_anchor_adjust_plan", "gsr_anchor_adjust_gather",
     "gsr_adam_step",
+    "gsr_depth_points", "gsr_point_normals",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -190,6 +191,10 @@ def load():
     lib.gsr_anchor_adjust_gather.argtypes = [_c_int] * 3 + [ctypes.POINTER(AdjustCopy), _vp, _vp, _c_int, _vp, _vp]
     lib.gsr_adam_step.restype = _c_int
     lib.gsr_adam_step.argtypes = [_c_int, ctypes.POINTER(AdamTensor), _vp]
+    lib.gsr_depth_points.restype = _c_int
+    lib.gsr_depth_points.argtypes = [_c_int, _c_int] + [_vp] * 5
+    lib.gsr_point_normals.restype = _c_int
+    lib.gsr_point_normals.argtypes = [_c_int, _c_int, _vp, _c_int, _c_float, ctypes.c_double, _vp, _vp]
     _lib = lib
     return lib
 

@@ -1046,3 +1046,30 @@ extern "C" int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, void
     GSR_HIP(adam_launch(n_tensors, tensors, (hipStream_t)stream), "adam step");
     return GSR_OK;
 }
+
+// ---- normals from rendered depth (normals.hip) ----
+static int normals_check_frame(const char* what, int H, int W)
+{
+    if (H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d (need both > 0)", what, H, W);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d has too many pixels (need H*W < 2^31 - 256)", what, H, W);
+    return GSR_OK;
+}
+
+extern "C" int gsr_depth_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, void* stream)
+{
+    if (int rc = normals_check_frame("depth points", H, W)) return rc;
+    if (!depth || !K || !c2w || !points) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth points: depth, K, c2w or points is NULL");
+    GSR_HIP(normals_launch_points(H, W, depth, K, c2w, points, (hipStream_t)stream), "depth points");
+    return GSR_OK;
+}
+
+extern "C" int gsr_point_normals(int H, int W, const float* points, int size, float gamma, double eps, float* normals, void* stream)
+{
+    if (int rc = normals_check_frame("point normals", H, W)) return rc;
+    if (size < 1 || size > 15 || size % 2 == 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: size=%d (need an odd size, 1 .. 15)", size);
+    if (!points || !normals) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: points or normals is NULL");
+    GSR_HIP(normals_launch_fit(H, W, points, size, gamma, eps, normals, (hipStream_t)stream), "point normals");
+    return GSR_OK;
+}

@@ -470,3 +470,7 @@ hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* co
 
 // adam.hip: one launch for all tensors (validated by the caller; tensors with n == 0 are skipped)
 hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_t stream);
+
+// normals.hip: depth -> point map, point map -> per-pixel plane-fit normals (both validated by the caller)
+hipError_t normals_launch_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, hipStream_t stream);
+hipError_t normals_launch_fit(int H, int W, const float* points, int size, float gamma, double eps, float* normals, hipStream_t stream);

@@ -446,6 +446,33 @@ typedef struct gsr_adam_tensor {
 int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors /* host */, void* stream /* hipStream_t */);
 
 /*
+ * Normals from rendered depth: the two functions render_set applies to every frame of the RGBD video (train.py:820-821).
+ *
+ * gsr_depth_points: depth2pcd_fromplane (train.py:252-267).  depth [H,W], K [3,3] and c2w [3,4] are fp32 DEVICE pointers (the caller
+ * holds K and c2w as tensors; nothing is read back); points is [3,H,W] fp32.  Per pixel (i, j), fp32, one rounding per operation,
+ * nothing contracts into an FMA:
+ *     xn = (j - K[0][2]) / K[0][0]     yn = (i - K[1][2]) / K[1][1]          (IEEE division)
+ *     xc = xn*d   yc = yn*d   zc = d
+ *     P[r] = ((c2w[r][0]*xc + c2w[r][1]*yc) + c2w[r][2]*zc) + c2w[r][3]      (summed left to right)
+ *
+ * gsr_point_normals: least_square_normal_regress_fast01 (train.py:270-298).  points [3,H,W] fp32 -> normals [H*W,3] fp32, row-major by
+ * pixel.  size is odd, 1 .. 15 (the reference uses 9); no workspace.  Per pixel with centre c and the size*size window points q taken
+ * with replicate padding (indices clamped to the image, which may be smaller than the window), rows then columns:
+ *     mask    q := (0,0,0)  iff  fabsf((q.z - c.z) / c.z) > gamma  in fp32, one rounding per operation: the reference's decision bit
+ *             for bit (only z decides; a NaN quotient keeps the point, an infinite one drops it; a zeroed point still counts as a row)
+ *     sums    A = sum q q^T (six entries) and s = sum q, accumulated in fp64 in window order
+ *     solve   det(A) in fp64 (Gaussian elimination with partial pivoting: the signed product of the pivots);  det < eps -> v = s (the
+ *             reference substitutes the identity), otherwise v = A^-1 s from the same elimination, fp64
+ *     output  v / max(|v|_2, 1e-12), a NaN component becomes 0, negated, rounded to fp32 once
+ * Both launch on `stream`, never synchronise and read nothing back; repeated calls give identical bits.  Rejected before launching
+ * (GSR_ERR_INVALID_ARGUMENT, text in gsr_last_error): NULL pointers, H or W <= 0, H*W >= 2^31 - 256, an even size or one outside 1 .. 15.
+ */
+int gsr_depth_points(int H, int W, const float* depth, const float* K /* [3,3] device */, const float* c2w /* [3,4] device */,
+                     float* points /* [3,H,W] */, void* stream /* hipStream_t */);
+int gsr_point_normals(int H, int W, const float* points /* [3,H,W] */, int size, float gamma, double eps, float* normals /* [H*W,3] */,
+                      void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
