@@ -12,7 +12,7 @@
 //
 // HBM traffic per Gaussian: read 48 B x traversed instances (the slots the backward blend actually wrote) + inputs;
 // write 12 + 12 + 4 + 4 + 12 + 12 + 16 = 72 B.
-#include "gsr_math.h"
+#include "gsr_scan.h"  // (and gsr_math.h through it)
 
 // DGR backward.cu:20-139 computeColorFromSH (bwd): returns dL/dmean contribution, writes dL/dsh.
 __device__ __forceinline__ float3 gsr_sh_backward(int idx, int deg, int M, float3 pos, const GsrCam& cam,
@@ -264,192 +264,69 @@ __device__ __forceinline__ void gsr_gauss_finish(const GsrGaussArgs& A, const in
 }
 
 #ifndef GSR_K7_WAVES
-#define GSR_K7_WAVES 4  // minimum waves per SIMD the register allocation has to leave room for
+#define GSR_K7_WAVES 4  // minimum waves per SIMD the one-wave kernel's register allocation has to leave room for
 #endif
-// LIGHT groups (at most GSR_K7_HEAVY_SLOTS gradient slots in the group's range): one wavefront per group.
-__global__ void __launch_bounds__(64, GSR_K7_WAVES) gsr_gauss_bwd_kernel(const GsrGaussArgs A)
+
+// The gradient slots of the 64 consecutive Gaussians from g0 on are one contiguous range [S0, S1) of `slots` (offsets[] is the
+// exclusive scan of the per-Gaussian slot counts).  Clamped to the slot count: a forward that binned nothing (num_slots = 0)
+// need not have produced offsets.
+__device__ __forceinline__ uint2 gsr_group_slots(const GsrGaussArgs& A, const int g0)
 {
-    // One wave per block owns 64 consecutive Gaussians; their gradient slots are one contiguous range [S0, S1) of
-    // `slots` (offsets[] is the exclusive scan of the per-Gaussian slot counts).  The backward blend writes a slot only
-    // for instances it traversed (slot_written[s] = 1; cleared by the forward's tile sort and left set here: which slots a backward
-    // writes depends on the forward state only, so a second backward over the same forward sets exactly the same flags): on the bench scene three quarters of the
-    // instances lie behind the depth where their tile saturates.  The wave therefore
-    //   1. reads the flag bytes of its range (coalesced), turns them into 64-bit masks + running counts (ballot),
-    //   2. builds the compact list of written slots and fetches only those, 3 lanes per 48-byte slot, into LDS,
-    //   3. lets every lane sum its own written slots out of LDS in ascending slot order (double accumulators).
-    // Three dependent memory round trips per wave; the per-Gaussian inputs of the second half are requested before any of it.
-    constexpr int BS = 64;
-    constexpr int FCH = 512;  // flags per pass (per-wave ranges average ~170 slots)
-    constexpr int WCH = 128;  // written slots staged per sub-pass (48 B each)
-    __shared__ float4 stage[WCH * 3];
-    __shared__ uint16_t wl[FCH];
-    const int P = A.P, num_slots = A.num_slots;
-    const uint32_t* __restrict__ offsets = A.offsets;
-    const float4* __restrict__ slots = A.slots;
-    const uint8_t* __restrict__ slot_written = A.slot_written;
-    const int lane = threadIdx.x;
-    const int g0 = blockIdx.x * BS;
-    const int idx = g0 + lane;
-    const bool live = idx < P;
-    const uint32_t cnt = live ? A.tiles[idx] : 0u;
-    // clamped to the slot count: a forward that binned nothing (num_slots = 0) need not have produced offsets
-    const uint32_t S1 = min((g0 + BS < P) ? offsets[g0 + BS] : (uint32_t)num_slots, (uint32_t)num_slots);
-    const uint32_t S0 = min(offsets[g0], S1);
-    if (S1 - S0 > GSR_K7_HEAVY_SLOTS) {  // a group with large splats (wave-uniform)
-        if (lane == 0 && A.heavy_seen) *A.heavy_seen = 1u;  // plain store, every such group writes the same value
-        if (!A.inline_heavy) {                              // listed for gsr_gauss_bwd_heavy_kernel
-            if (lane == 0) A.heavy[16 + atomicAdd(&A.heavy[0], 1u)] = (uint32_t)blockIdx.x;
-            return;
-        }
-        // no heavy kernel was launched (the host had seen no heavy group in its previous backward): done here, window by
-        // window on one wave -- same bits, slow, and only until the next call, which the store above switches over
-    }
-    const bool vis = live && A.radii[idx] > 0;
-    const uint32_t off = live ? offsets[idx] : 0u;
-    // early requests for the per-Gaussian half (independent of the slot phase)
-    float3 m = make_float3(0.f, 0.f, 0.f), sc = make_float3(0.f, 0.f, 0.f);
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vis) {
-        m = make_float3(A.means3D[3 * idx], A.means3D[3 * idx + 1], A.means3D[3 * idx + 2]);
-        if (!A.cov3D_precomp) {
-            sc = make_float3(A.scales[3 * idx], A.scales[3 * idx + 1], A.scales[3 * idx + 2]);
-            q = reinterpret_cast<const float4*>(A.rotations)[idx];
-        }
-    }
-    double acc[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };  // the per-tile partials are summed in double, rounded once
-    uint32_t any_written = 0;                              // (wave-uniform) some slot of the group was written
-    // Waves that hold a Gaussian with more than 24 slots spread the summation over the lanes as (Gaussian, field) tasks
-    // instead of letting that Gaussian's lane walk all its slots 11 fields at a time while 63 lanes wait: 11 consecutive
-    // lanes share a Gaussian, each sums one field in the same ascending order (so both schemes give the same bits).
-    // Wave-uniform choice from the slot counts.  The per-lane task sums stay in registers, acc[k] for task k * 64 + lane;
-    // one transposition through LDS -- aliased onto `stage`, which is free by then -- hands every Gaussian's 11 sums to
-    // its own lane.
-    double* accG = reinterpret_cast<double*>(stage);
-    static_assert(sizeof(double) * BS * 11 <= sizeof(float4) * WCH * 3, "accG must fit into the staging buffer");
-    __shared__ uint32_t sCi0[BS], sCi1[BS];
-    uint32_t cmax = cnt;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, d, 64));
-    const bool spread = cmax > 24u;
-    for (uint32_t base = S0, nf; base < S1; base += nf) {
-        // One 8-byte load per lane covers the 512 flag bytes from the 8-aligned address below `base` (every pass but the
-        // first starts aligned); lane l holds the flags of slots base - shift + 8 l + k, k = 0..7, as bit k of m.
-        const uint32_t shift = base & 7u;
-        nf = min(S1 - base, (uint32_t)FCH - shift);
-        uint2 w8 = make_uint2(0u, 0u);
-        if (8u * lane < shift + nf) w8 = *reinterpret_cast<const uint2*>(slot_written + (base - shift) + 8u * lane);
-        // bytes are 0 / 1: a multiplication gathers the four low bits of a word's bytes in its top byte
-        uint32_t m = (((w8.x & 0x01010101u) * 0x01020408u) >> 24) | ((((w8.y & 0x01010101u) * 0x01020408u) >> 24) << 4);
-        {
-            const int lo_k = min(max((int)shift - 8 * lane, 0), 8), hi_k = min(max((int)(shift + nf) - 8 * lane, 0), 8);
-            m &= ((1u << hi_k) - 1u) & ~((1u << lo_k) - 1u);  // slots of the neighbouring groups / behind the range
-        }
-        const uint32_t c = (uint32_t)__popc(m), incl = gsr_wave_scan_add(c), excl = incl - c;
-        const uint32_t run = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            if ((m >> k) & 1u) wl[excl + (uint32_t)__popc(m & ((1u << k) - 1u))] = (uint16_t)(8 * lane + k - (int)shift);
-        __syncthreads();
-        // A lane's written slots are consecutive entries [ci0, ci1) of the compact list: ci = number of written slots
-        // of the pass below the lane's first / past its last slot (the owner lane's running count + the set bits below the
-        // position, fetched with one cross-lane read each).  No flag test is left in the summation loop.
-        const uint32_t lo = min(max(off, base), base + nf) - base, hi = min(max(off + cnt, base), base + nf) - base;
-        const uint32_t pk = (excl << 8) | m;
-        uint32_t ci0, ci1;
-        {
-            const uint32_t a0 = lo + shift, a1 = hi + shift;
-            const uint32_t p0 = (uint32_t)__shfl((int)pk, (int)min(a0 >> 3, 63u), 64), p1 = (uint32_t)__shfl((int)pk, (int)min(a1 >> 3, 63u), 64);
-            ci0 = lo < nf ? (p0 >> 8) + (uint32_t)__popc(p0 & 0xffu & ((1u << (a0 & 7u)) - 1u)) : run;
-            ci1 = hi < nf ? (p1 >> 8) + (uint32_t)__popc(p1 & 0xffu & ((1u << (a1 & 7u)) - 1u)) : run;
-        }
-        any_written |= run;
-        for (uint32_t w0 = 0; w0 < run; w0 += WCH) {
-            const uint32_t nw = min(run - w0, (uint32_t)WCH);
-            float4 v[WCH * 3 / 64];
-#pragma unroll
-            for (int k = 0; k < WCH * 3 / 64; k++) {
-                const uint32_t i = lane + k * 64;
-                v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (i < nw * 3) v[k] = slots[(size_t)(base + wl[w0 + i / 3]) * 3 + i % 3];
-            }
-#pragma unroll
-            for (int k = 0; k < WCH * 3 / 64; k++) stage[lane + k * 64] = v[k];
-            __syncthreads();
-            if (spread) {
-                if (w0 == 0) { sCi0[lane] = ci0; sCi1[lane] = ci1; }
-                __syncthreads();
-                const float* sf = reinterpret_cast<const float*>(stage);
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const int task = k * BS + lane, g = task / 11, v = task - g * 11;
-                    const uint32_t e0 = max(sCi0[g], w0), e1 = min(sCi1[g], w0 + nw);
-                    if (e1 > e0) gsr_sum_entries(acc[k], sf + (e0 - w0) * 12 + v, e1 - e0);
-                }
-            } else {
-                const uint32_t e0 = max(ci0, w0), e1 = min(ci1, w0 + nw);
-                for (uint32_t e = e0; e < e1; e++) {
-                    const float4 a = stage[(e - w0) * 3], b = stage[(e - w0) * 3 + 1], c = stage[(e - w0) * 3 + 2];
-                    acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-                    acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
-                    acc[8] += c.x; acc[9] += c.y; acc[10] += c.z;
-                }
-            }
-            __syncthreads();
-        }
-        __syncthreads();
-    }
-    if (spread) {  // transpose: task sums (k * 64 + lane) -> the 11 sums of Gaussian `lane`
-#pragma unroll
-        for (int k = 0; k < 11; k++) accG[k * BS + lane] = acc[k];
-        __syncthreads();
-#pragma unroll
-        for (int v = 0; v < 11; v++) acc[v] = accG[lane * 11 + v];
-    }
-    if (!live) return;
-    // A group none of whose slots was written (wave-uniform: every Gaussian of it culled, or behind the depth its tiles are walked to):
-    // all eleven sums of all its lanes are zero and every row is an exact zero -- the second half is skipped.  (Round 6: in storage order
-    // a trained scene keeps the offsets of an anchor, and mostly neighbouring anchors, next to each other, so whole groups are hidden
-    // together; the synthetic bench cloud is stored in random order and has no such group: see DESIGN 11 for the compaction
-    // experiments that tried to get the same saving there.)
-    gsr_gauss_finish(A, idx, vis && any_written != 0u, acc, m, sc, q);
+    const uint32_t S1 = min((g0 + 64 < A.P) ? A.offsets[g0 + 64] : (uint32_t)A.num_slots, (uint32_t)A.num_slots);
+    return make_uint2(min(A.offsets[g0], S1), S1);
 }
 
-// HEAVY groups (more than GSR_K7_HEAVY_SLOTS gradient slots: a splat can cover thousands of tiles): four wavefronts per group.  A lone wave has ~6 KB of slot data in flight per memory round trip and walks a dense range of
-// thousands of slots window by window (measured on a scene of large splats: the launch lasted 347 us, of which ~35 us'
-// worth was arithmetic -- the rest was the few waves that own the big front splats).  Here the four waves scan 2048 flags
-// per pass, gather four 128-slot windows per round trip and sum them as (Gaussian, field) tasks spread over all 256
-// threads, each task in ascending slot order -- the same order, hence the same bits, as the one-wave scheme.  Wave 0
-// then runs the second half for the 64 Gaussians.
-__global__ void __launch_bounds__(256) gsr_gauss_bwd_heavy_kernel(const GsrGaussArgs A)
+// LDS of one group walk by NW waves.
+template <int NW>
+struct GsrSlotLds {
+    float4 stage[NW * 128 * 3];      // one window of 128 written slots (48 B each) per wave, contiguous; NW = 4: 24 KiB
+    uint16_t wl[NW * 512];           // the compact list of a pass: written slots, relative to the pass's first slot
+    uint32_t ci0[64], ci1[64];       // a Gaussian's interval in that list
+    uint32_t pk[NW > 1 ? NW * 64 : 1];  // NW > 1: every thread's (exclusive count << 8 | flag mask) word
+};
+
+// The walk of one group of 64 consecutive Gaussians (from g0, slots S = gsr_group_slots(A, g0)) by the NW waves of a workgroup,
+// all of which must make the call: the sums of the group's written gradient slots, then, on wave 0, gsr_gauss_finish for each
+// Gaussian.  (S is the caller's: the one-wave kernel has it from its heavy test, and behind that test's stores the compiler
+// would fetch the two offsets a second time, one more round trip in front of the three below.)
+//
+// The backward blend writes a slot only for instances it traversed (slot_written[s] = 1; cleared by the forward's tile sort and
+// left set here: which slots a backward writes depends on the forward state only, so a second backward over the same forward
+// sets exactly the same flags): on the bench scene three quarters of the instances lie behind the depth where their tile
+// saturates.  The NT = 64 NW threads therefore
+//   1. read the flag bytes of the range, FCH = 8 NT per pass (coalesced; one-wave ranges average ~170 slots), and turn them
+//      into 8-bit masks + running counts,
+//   2. build the compact list of written slots and fetch only those, one window of WCH = 128 per wave and round, 3 lanes per
+//      48-byte slot, into LDS,
+//   3. sum every Gaussian's written slots out of LDS in ascending slot order (double accumulators, rounded once).
+// Three dependent memory round trips; the per-Gaussian inputs of the second half are requested before any of it.
+//
+// The summation is spread over the threads as (Gaussian, field) tasks, task k NT + t -> Gaussian task / 11, field task % 11,
+// 704 tasks, NTASK per thread: 11 consecutive threads share a Gaussian, each sums one field.  The task sums stay in registers,
+// acc[k]; one transposition through LDS -- aliased onto the staging buffer, which is free by then -- hands every Gaussian's 11
+// sums to its lane of wave 0.  One wave alone (NW = 1) does so only when it holds a Gaussian with more than 24 slots, instead
+// of letting that Gaussian's lane walk all its slots 11 fields at a time while 63 lanes wait (wave-uniform choice from the
+// slot counts); otherwise every lane sums its own Gaussian's slots.  Each sum runs over the same slots in the same ascending
+// order whatever NW, the pass and window boundaries and the scheme: the same bits in every mode.
+template <int NW>
+__device__ __forceinline__ void gsr_gauss_group(const GsrGaussArgs& A, const int g0, const uint2 S, GsrSlotLds<NW>& L)
 {
-    constexpr int BS = 64, NW = 4, NT = 256;
-    constexpr int FCH = 2048;      // flags per pass: 8 per thread
-    constexpr int NG = FCH / 64;   // 64-flag groups per pass
-    constexpr int WCH = 128;       // written slots per wave and round
-    __shared__ float4 stage[NW * WCH * 3];  // 24 KiB: four windows, contiguous
-    __shared__ uint16_t wl[FCH];
-    __shared__ unsigned long long gmask[NG];
-    __shared__ uint32_t gcnt[NG], gbase[NG + 1];
-    __shared__ uint32_t sCi0[BS], sCi1[BS];
-    const int P = A.P, num_slots = A.num_slots;
-    const uint32_t* __restrict__ offsets = A.offsets;
+    constexpr int BS = 64, NT = BS * NW;
+    constexpr int FCH = 8 * NT;  // flags per pass
+    constexpr int WCH = 128;     // written slots per wave and round
+    constexpr int NTASK = (BS * 11 + NT - 1) / NT;
+    static_assert(sizeof(double) * BS * 11 <= sizeof(L.stage), "accG must fit into the staging buffer");
+    double* accG = reinterpret_cast<double*>(L.stage);
     const float4* __restrict__ slots = A.slots;
-    uint8_t* __restrict__ slot_written = A.slot_written;
+    const uint8_t* __restrict__ slot_written = A.slot_written;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint32_t nheavy = A.heavy[0];  // the groups gsr_gauss_bwd_kernel listed (any order: groups are independent)
-    if (blockIdx.x == 0 && t == 0 && A.heavy_seen) *A.heavy_seen = 2u + nheavy;  // (after every store of the first kernel: stream order)
-    __shared__ uint32_t s_next;
-    // the first gridDim.x groups are dealt by block index, the rest is fetched from a counter as workgroups come free
-    // (groups differ in size by an order of magnitude; a few hundred fetches per launch: the counter is not a bottleneck)
-    for (uint32_t it = blockIdx.x; it < nheavy;) {
-    const int g0 = (int)A.heavy[16 + it] * BS;
     const int idx = g0 + lane;  // every wave looks at the same 64 Gaussians
-    const bool live = idx < P;
-    const uint32_t S1 = min((g0 + BS < P) ? offsets[g0 + BS] : (uint32_t)num_slots, (uint32_t)num_slots);
-    const uint32_t S0 = min(offsets[g0], S1);
+    const bool live = idx < A.P;
+    const uint32_t S1 = S.y;
     const uint32_t cnt = live ? A.tiles[idx] : 0u;
     const bool vis = live && A.radii[idx] > 0;
-    const uint32_t off = live ? offsets[idx] : 0u;
+    const uint32_t off = live ? A.offsets[idx] : 0u;
+    // early requests for the per-Gaussian half (independent of the slot phase)
     float3 m = make_float3(0.f, 0.f, 0.f), sc = make_float3(0.f, 0.f, 0.f);
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
     if (vis && wave == 0) {
@@ -459,90 +336,149 @@ __global__ void __launch_bounds__(256) gsr_gauss_bwd_heavy_kernel(const GsrGauss
             q = reinterpret_cast<const float4*>(A.rotations)[idx];
         }
     }
-    // (Gaussian, field) tasks: task k * 256 + t -> Gaussian task / 11, field task % 11; 704 tasks over 256 threads
-    double tacc[3] = { 0, 0, 0 };
-    int tg[3], tv[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const int task = k * NT + t;
-        tg[k] = task < BS * 11 ? task / 11 : -1;
-        tv[k] = task - (task / 11) * 11;
-    }
-    for (uint32_t base = S0; base < S1; base += FCH) {
-        const uint32_t nf = min(S1 - base, (uint32_t)FCH);
-        uint8_t f[FCH / NT];
-#pragma unroll
-        for (int k = 0; k < FCH / NT; k++) {
-            const uint32_t i = k * NT + t;
-            f[k] = i < nf ? slot_written[base + i] : (uint8_t)0;
+    double acc[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };  // task sums (the first NTASK) or the lane's own 11 sums
+    uint32_t any_written = 0;                              // (uniform) some slot of the group was written
+    const bool spread = NW > 1 || gsr_wave_max(cnt) > 24u;
+    for (uint32_t base = S.x, nf; base < S1; base += nf) {
+        // One 8-byte load per thread covers the FCH flag bytes from the 8-aligned address below `base` (every pass but the
+        // first starts aligned); thread t holds the flags of slots base - shift + 8 t + k, k = 0..7, as bit k of fm.
+        const uint32_t shift = base & 7u;
+        nf = min(S1 - base, (uint32_t)FCH - shift);
+        uint2 w8 = make_uint2(0u, 0u);
+        if (8u * t < shift + nf) w8 = *reinterpret_cast<const uint2*>(slot_written + (base - shift) + 8u * t);
+        // bytes are 0 / 1: a multiplication gathers the four low bits of a word's bytes in its top byte
+        uint32_t fm = (((w8.x & 0x01010101u) * 0x01020408u) >> 24) | ((((w8.y & 0x01010101u) * 0x01020408u) >> 24) << 4);
+        {
+            const int lo_k = min(max((int)shift - 8 * t, 0), 8), hi_k = min(max((int)(shift + nf) - 8 * t, 0), 8);
+            fm &= ((1u << hi_k) - 1u) & ~((1u << lo_k) - 1u);  // slots of the neighbouring groups / behind the range
         }
-        unsigned long long mk[FCH / NT];
-#pragma unroll
-        for (int k = 0; k < FCH / NT; k++) {
-            mk[k] = __ballot(f[k] != 0);
-            if (lane == 0) { gmask[k * NW + wave] = mk[k]; gcnt[k * NW + wave] = (uint32_t)__popcll(mk[k]); }  // group = 64 consecutive flags
+        const uint32_t c = (uint32_t)__popc(fm);
+        uint32_t excl, run;  // written slots of the pass below the thread's eight; in the whole pass (uniform)
+        if constexpr (NW == 1) {
+            const uint32_t incl = gsr_wave_scan_add(c);
+            excl = incl - c;
+            run = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        } else {
+            excl = gsr_block_scan_excl<NT>(c, &run);  // (its one barrier; the loop's own lie between two calls)
+            run = (uint32_t)__builtin_amdgcn_readfirstlane((int)run);
         }
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if ((fm >> k) & 1u) L.wl[excl + (uint32_t)__popc(fm & ((1u << k) - 1u))] = (uint16_t)(8 * t + k - (int)shift);
+        const uint32_t pk = (excl << 8) | fm;
+        if constexpr (NW > 1) L.pk[t] = pk;
         __syncthreads();
-        if (t <= NG) {  // exclusive prefix of the 32 group counts (ascending slot order); gbase[NG] = written slots of the pass
-            uint32_t s = 0;
-            for (int g = 0; g < t; g++) s += gcnt[g];
-            gbase[t] = s;
-        }
-        __syncthreads();
-        const uint32_t run = gbase[NG];
-#pragma unroll
-        for (int k = 0; k < FCH / NT; k++)
-            if (f[k]) wl[gbase[k * NW + wave] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk[k], 0u))] = (uint16_t)(k * NT + t);
-        if (wave == 0) {  // a Gaussian's written slots = entries [ci0, ci1) of the pass's compact list
+        // A Gaussian's written slots are consecutive entries [ci0, ci1) of the compact list: ci = number of written slots
+        // of the pass below its first / past its last slot (the owner thread's running count + the set bits below the
+        // position, fetched with one cross-thread read each).  No flag test is left in the summation loop.
+        uint32_t ci0 = 0, ci1 = 0;
+        if (wave == 0) {
             const uint32_t lo = min(max(off, base), base + nf) - base, hi = min(max(off + cnt, base), base + nf) - base;
-            uint32_t ci0 = run, ci1 = run;
-            if (lo < nf) ci0 = gbase[lo >> 6] + (uint32_t)__popcll(gmask[lo >> 6] & ((1ull << (lo & 63)) - 1ull));
-            if (hi < nf) ci1 = gbase[hi >> 6] + (uint32_t)__popcll(gmask[hi >> 6] & ((1ull << (hi & 63)) - 1ull));
-            sCi0[lane] = ci0; sCi1[lane] = ci1;
+            const uint32_t a0 = lo + shift, a1 = hi + shift;
+            const int t0 = (int)min(a0 >> 3, (uint32_t)NT - 1u), t1 = (int)min(a1 >> 3, (uint32_t)NT - 1u);
+            uint32_t p0, p1;
+            if constexpr (NW == 1) { p0 = (uint32_t)__shfl((int)pk, t0, 64); p1 = (uint32_t)__shfl((int)pk, t1, 64); }
+            else { p0 = L.pk[t0]; p1 = L.pk[t1]; }
+            ci0 = lo < nf ? (p0 >> 8) + (uint32_t)__popc(p0 & 0xffu & ((1u << (a0 & 7u)) - 1u)) : run;
+            ci1 = hi < nf ? (p1 >> 8) + (uint32_t)__popc(p1 & 0xffu & ((1u << (a1 & 7u)) - 1u)) : run;
+            if (spread) { L.ci0[lane] = ci0; L.ci1[lane] = ci1; }  // read behind the staging barrier of the first round
         }
-        __syncthreads();
+        any_written |= run;
         for (uint32_t w0 = 0; w0 < run; w0 += NW * WCH) {
-            const uint32_t nall = min(run - w0, (uint32_t)(NW * WCH));   // entries of this round
-            const uint32_t wb = (uint32_t)wave * WCH;                    // this wave's window inside the round
+            const uint32_t nall = min(run - w0, (uint32_t)(NW * WCH));  // entries of this round
+            const uint32_t wb = (uint32_t)wave * WCH;                   // this wave's window inside the round
             const uint32_t nw = wb < nall ? min(nall - wb, (uint32_t)WCH) : 0u;
-            float4 v[WCH * 3 / 64];
+            float4 v[WCH * 3 / 64];  // loads before LDS stores: all of a window's requests in flight together
 #pragma unroll
             for (int k = 0; k < WCH * 3 / 64; k++) {
                 const uint32_t i = lane + k * 64;
                 v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (i < nw * 3) v[k] = slots[(size_t)(base + wl[w0 + wb + i / 3]) * 3 + i % 3];
+                if (i < nw * 3) v[k] = slots[(size_t)(base + L.wl[w0 + wb + i / 3]) * 3 + i % 3];
             }
 #pragma unroll
-            for (int k = 0; k < WCH * 3 / 64; k++) stage[wb * 3 + lane + k * 64] = v[k];
+            for (int k = 0; k < WCH * 3 / 64; k++) L.stage[wb * 3 + lane + k * 64] = v[k];
             __syncthreads();
-            const float* sf = reinterpret_cast<const float*>(stage);
+            if (spread) {
+                const float* sf = reinterpret_cast<const float*>(L.stage);
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                if (tg[k] < 0) continue;
-                const uint32_t e0 = max(sCi0[tg[k]], w0), e1 = min(sCi1[tg[k]], w0 + nall);
-                if (e1 > e0) gsr_sum_entries(tacc[k], sf + (e0 - w0) * 12 + tv[k], e1 - e0);
+                for (int k = 0; k < NTASK; k++) {
+                    const int task = k * NT + t, g = task / 11, f = task - g * 11;
+                    if (NTASK * NT > BS * 11 && task >= BS * 11) continue;
+                    const uint32_t e0 = max(L.ci0[g], w0), e1 = min(L.ci1[g], w0 + nall);
+                    if (e1 > e0) gsr_sum_entries(acc[k], sf + (e0 - w0) * 12 + f, e1 - e0);
+                }
+            } else {
+                const uint32_t e0 = max(ci0, w0), e1 = min(ci1, w0 + nall);
+                for (uint32_t e = e0; e < e1; e++) {
+                    const float4 a = L.stage[(e - w0) * 3], b = L.stage[(e - w0) * 3 + 1], c = L.stage[(e - w0) * 3 + 2];
+                    acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
+                    acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
+                    acc[8] += c.x; acc[9] += c.y; acc[10] += c.z;
+                }
             }
             __syncthreads();
         }
         __syncthreads();
     }
-    // task sums -> the 11 sums of Gaussian `lane` (through LDS, aliased onto the staging buffer, which is free now)
-    double* accG = reinterpret_cast<double*>(stage);
-    static_assert(sizeof(double) * BS * 11 <= sizeof(float4) * NW * WCH * 3, "accG must fit into the staging buffer");
+    if (spread) {  // transpose: task sums (k NT + t) -> the 11 sums of Gaussian `lane`, on wave 0
 #pragma unroll
-    for (int k = 0; k < 3; k++)
-        if (tg[k] >= 0) accG[k * NT + t] = tacc[k];
-    __syncthreads();
-    if (wave == 0 && live) {
-        double acc[11];
+        for (int k = 0; k < NTASK; k++)
+            if (NTASK * NT == BS * 11 || k * NT + t < BS * 11) accG[k * NT + t] = acc[k];
+        __syncthreads();
+        if (wave == 0) {
 #pragma unroll
-        for (int v = 0; v < 11; v++) acc[v] = accG[lane * 11 + v];
-        gsr_gauss_finish(A, idx, vis, acc, m, sc, q);
+            for (int f = 0; f < 11; f++) acc[f] = accG[lane * 11 + f];
+        }
     }
-    if (t == 0) s_next = gridDim.x + atomicAdd(&A.heavy[1], 1u);
-    __syncthreads();  // also: the next group's staging must not overtake wave 0's reads of accG
-    it = s_next;
-    __syncthreads();
+    // A group none of whose slots was written (wave-uniform: every Gaussian of it culled, or behind the depth its tiles are walked to):
+    // all eleven sums of all its Gaussians are zero and every row is a zero -- the one-wave kernel skips the second half.  (Round 6: in
+    // storage order a trained scene keeps the offsets of an anchor, and mostly neighbouring anchors, next to each other, so whole groups
+    // are hidden together; the synthetic bench cloud is stored in random order and has no such group: see DESIGN 11 for the compaction
+    // experiments that tried to get the same saving there.)  The cooperative kernel never skipped it, and its zeros are not all the
+    // skipped rows' +0: products of a zero sum with negative factors leave -0 in dL_dscales and dL_drotations.  Those bits are kept.
+    const bool skip = NW == 1 && any_written == 0u;
+    if (wave == 0 && live) gsr_gauss_finish(A, idx, vis && !skip, acc, m, sc, q);
+}
+
+// LIGHT groups (at most GSR_K7_HEAVY_SLOTS gradient slots in the group's range): one wavefront per group.
+__global__ void __launch_bounds__(64, GSR_K7_WAVES) gsr_gauss_bwd_kernel(const GsrGaussArgs A)
+{
+    __shared__ GsrSlotLds<1> L;
+    const int g0 = blockIdx.x * 64;
+    const uint2 S = gsr_group_slots(A, g0);
+    if (S.y - S.x > GSR_K7_HEAVY_SLOTS) {  // a group with large splats (wave-uniform)
+        if (threadIdx.x == 0 && A.heavy_seen) *A.heavy_seen = 1u;  // plain store, every such group writes the same value
+        if (!A.inline_heavy) {                                     // listed for gsr_gauss_bwd_heavy_kernel
+            if (threadIdx.x == 0) A.heavy[16 + atomicAdd(&A.heavy[0], 1u)] = (uint32_t)blockIdx.x;
+            return;
+        }
+        // no heavy kernel was launched (the host had seen no heavy group in its previous backward): done here, window by
+        // window on one wave -- same bits, slow, and only until the next call, which the store above switches over
+    }
+    gsr_gauss_group<1>(A, g0, S, L);
+}
+
+// HEAVY groups (more than GSR_K7_HEAVY_SLOTS gradient slots: a splat can cover thousands of tiles): four wavefronts per
+// group.  A lone wave has ~6 KB of slot data in flight per memory round trip and walks a dense range of thousands of slots
+// window by window (measured on a scene of large splats: the launch lasted 347 us, of which ~35 us' worth was arithmetic --
+// the rest was the few waves that own the big front splats).  Here the four waves scan 2048 flags per pass, gather four
+// 128-slot windows per round trip and sum them as tasks spread over all 256 threads; wave 0 then runs the second half for
+// the 64 Gaussians.
+__global__ void __launch_bounds__(256) gsr_gauss_bwd_heavy_kernel(const GsrGaussArgs A)
+{
+    __shared__ GsrSlotLds<4> L;
+    __shared__ uint32_t s_next;
+    const uint32_t nheavy = A.heavy[0];  // the groups gsr_gauss_bwd_kernel listed (any order: groups are independent)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && A.heavy_seen) *A.heavy_seen = 2u + nheavy;  // (after every store of the first kernel: stream order)
+    // the first gridDim.x groups are dealt by block index, the rest is fetched from a counter as workgroups come free
+    // (groups differ in size by an order of magnitude; a few hundred fetches per launch: the counter is not a bottleneck)
+    for (uint32_t it = blockIdx.x; it < nheavy;) {
+        const int g0 = (int)A.heavy[16 + it] * 64;
+        gsr_gauss_group<4>(A, g0, gsr_group_slots(A, g0), L);
+        if (threadIdx.x == 0) s_next = gridDim.x + atomicAdd(&A.heavy[1], 1u);
+        __syncthreads();  // also: the next group's staging must not overtake wave 0's reads of accG
+        it = s_next;
+        __syncthreads();
     }
 }
 

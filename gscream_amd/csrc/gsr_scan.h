@@ -1,5 +1,6 @@
 // gsr_scan.h -- the scans and the ordered compaction ("count, scan, place") of the kernels around the rasterizer: decode,
-// kNN, anchor growth, anchor sampling -- and of the rasterizer's binning (binning.hip: gsr_block_scan_runs and the C = 4 form).
+// kNN, anchor growth, anchor sampling -- and of the rasterizer's binning (binning.hip: gsr_block_scan_runs and the C = 4 form) and per-Gaussian
+// backward (gauss_bwd.hip: the written-slot counts of a flag pass across the cooperative kernel's four waves, gsr_wave_max).
 // Integer sums only, with one fixed association order per output element.  (gsr_fwd_order_block keeps its own scan.)
 //
 // The block-wide forms keep their per-wave totals in a static LDS array and hold exactly ONE barrier: a kernel that calls

@@ -1,0 +1,210 @@
+"""The per-Gaussian backward's group walk (gauss_bwd.hip: gsr_gauss_group, one wave or four per group of 64 Gaussians) on the
+smallest scenes that reach each way it can go: more than one flag pass and window round, both summation schemes, an unaligned
+start, sparse and absent flags, the heavy threshold, P < 64 and no slots at all.
+
+With tile culling off the lists are the reference's, so the oracle's state predicts the walk exactly: a Gaussian owns
+tiles_touched slots, and a slot is written when its instance lies in front of the deepest n_contrib of its tile.  Every scene's
+census is asserted from that state (conditions on the scene, not tolerances), then the gradients are checked against the oracle
+and for bit-equality between the automatic mode, everything on one wave, and the cooperative kernel.  (Bit-equality, signs of
+zeros included: only a HEAVY group with no written slot at all would tell the kernels apart, the one-wave kernel skipping its second
+half and writing +0 where the cooperative kernel's products leave some -0; every heavy group here has written slots.)"""
+import os
+import sys
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import helpers as Hh  # noqa: E402
+from gscream_amd import set_tuning  # noqa: E402
+from gscream_amd import synthetic as S  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+NT = max(1, min(16, os.cpu_count() or 1))  # oracle threads
+HEAVY_SLOTS = 1024                         # GSR_K7_HEAVY_SLOTS: a group is heavy when it owns MORE slots than this
+FLAG_PASS = 512                            # flags per pass of one wave
+
+
+@pytest.fixture(autouse=True)
+def _default_tuning():
+    set_tuning()
+    yield
+    set_tuning()
+
+
+def _f32(a):
+    return np.asarray(a, np.float32)
+
+
+def equal_splats():
+    s = S.scene_config1(seed=94, P=150, W=160, H=128)
+    rng = np.random.default_rng(13)
+    s["means3D"][:, 2] = 4.0
+    s["means3D"][:, 0] = _f32(rng.uniform(-1.6, 1.6, size=150))
+    s["means3D"][:, 1] = _f32(rng.uniform(-1.2, 1.2, size=150))
+    s["opacities"][:] = _f32(rng.uniform(0.02, 0.2, size=(150, 1)))
+    s["scales"][:] = 0.12
+    return s
+
+
+def mixed_splats():
+    s = S.scene_config1(seed=91, P=200, W=160, H=128)
+    rng = np.random.default_rng(7)
+    s["scales"][:] = _f32(rng.uniform(0.12, 0.18, size=(200, 3)))
+    s["opacities"][:] = _f32(rng.uniform(0.02, 0.3, size=(200, 1)))
+    return s
+
+
+def wall():
+    s = S.scene_config1(seed=93, P=256, W=96, H=64)
+    rng = np.random.default_rng(11)
+    s["means3D"][:64, 2] = _f32(rng.uniform(2.0, 2.3, size=64))
+    s["means3D"][:64, 0] = _f32(rng.uniform(-0.8, 0.8, size=64))
+    s["means3D"][:64, 1] = _f32(rng.uniform(-0.5, 0.5, size=64))
+    s["scales"][:64] = 1.5
+    s["opacities"][:64] = 1.0
+    s["means3D"][128:192, 2] = _f32(rng.uniform(5.0, 6.0, size=64))
+    s["means3D"][128:192, 0] = _f32(rng.uniform(-1.0, 1.0, size=64))
+    s["means3D"][128:192, 1] = _f32(rng.uniform(-0.6, 0.6, size=64))
+    s["scales"][128:192] = 0.05
+    return s
+
+
+def huge_gaussians():
+    """The scene of test_gpu_parity.py::test_more_cases_against_live_oracle[huge_gaussians]."""
+    rng = np.random.default_rng(zlib.crc32(b"huge_gaussians") % 1000)
+    s = S.scene_config1(seed=85, P=300, W=320, H=256)
+    s["scales"][:40] = _f32(rng.uniform(0.8, 2.5, size=(40, 3)))
+    s["opacities"][:40] = _f32(rng.uniform(0.02, 0.6, size=(40, 1)))
+    return s
+
+
+def tiny():
+    return S.scene_config1(seed=92, P=37, W=64, H=48)
+
+
+def tiny_behind():
+    s = tiny()
+    s["means3D"][:, 2] = -s["means3D"][:, 2]  # every Gaussian behind the camera: nothing is rendered
+    return s
+
+
+def census(s, st):
+    """Per group of 64 consecutive Gaussians: gradient slots owned and slots the backward blend writes (culling off), and the
+    largest slot count of a single Gaussian in the group -- from the oracle's state alone."""
+    P = s["means3D"].shape[0]
+    G = (P + 63) // 64
+    tt = np.zeros(G * 64, np.int64)
+    tt[:P] = np.asarray(st["tiles_touched"], np.int64)
+    gx, gy = (s["W"] + 15) // 16, (s["H"] + 15) // 16
+    nc = np.zeros((gy * 16, gx * 16), np.int64)
+    nc[:s["H"], :s["W"]] = np.asarray(st["n_contrib"], np.int64).reshape(s["H"], s["W"])
+    deepest = nc.reshape(gy, 16, gx, 16).max(axis=(1, 3)).reshape(-1)
+    ranges = np.asarray(st["ranges"], np.int64).reshape(-1, 2)
+    pl = np.asarray(st["point_list"], np.int64)
+    written = np.zeros(G, np.int64)
+    for tile in range(gx * gy):
+        r0 = ranges[tile, 0]
+        assert deepest[tile] <= ranges[tile, 1] - r0
+        written += np.bincount(pl[r0:r0 + deepest[tile]] // 64, minlength=G)
+    offs = np.concatenate([[0], np.cumsum(tt)[:-1]])
+    return dict(slots=tt.reshape(G, 64).sum(1), written=written, most=tt.reshape(G, 64).max(1), starts=offs[::64],
+                offs=offs, counts=tt)
+
+
+def _check_equal_splats(c):
+    assert c["slots"].tolist() == [540, 525, 183] and c["written"].tolist() == [537, 518, 159] and c["most"].max() == 9
+    # two flag passes on one wave, several window rounds, per-lane summation only, an unaligned start, a tail group of 22
+    assert (c["slots"][:2] > FLAG_PASS).all() and (c["written"][:2] > 4 * 128).all() and c["most"].max() <= 24
+    assert c["starts"][1] % 8 == 4
+
+
+def _check_mixed_splats(c):
+    assert c["slots"].tolist() == [556, 588, 666, 78] and c["most"].max() == 36
+    # two passes in the task mode; with up to 36 slots each, Gaussians straddle the pass boundary at 512 flags
+    assert (c["slots"][:3] > FLAG_PASS).all() and (c["most"][:3] > 24).all() and (c["slots"] <= HEAVY_SLOTS).all()
+    for g in range(3):  # (a wave's first pass ends at the 512th flag from the 8-aligned address below its first slot)
+        end = c["starts"][g] - c["starts"][g] % 8 + FLAG_PASS
+        assert ((c["offs"] < end) & (end < c["offs"] + c["counts"])).any(), f"group {g}: no Gaussian straddles the pass boundary"
+
+
+def _check_wall(c):
+    assert c["slots"].tolist() == [1536, 187, 131, 166] and c["written"].tolist() == [107, 0, 0, 0]
+    # a heavy group with fewer than a tenth of its slots written; whole groups that own slots of which none is written
+    assert c["slots"][0] > HEAVY_SLOTS and 10 * c["written"][0] < c["slots"][0]
+    assert (c["slots"][1:] > 0).all() and not c["written"][1:].any()
+
+
+def _check_huge_gaussians(c):
+    assert c["slots"].tolist()[:4] == [13095, 1038, 1291, 1024]
+    # seven passes of 2048 flags; two groups just beyond the threshold; one of exactly 1024, which is light: the threshold is strict
+    assert c["slots"][0] > 6 * 2048 and (c["slots"][1:3] > HEAVY_SLOTS).all() and c["slots"][3] == HEAVY_SLOTS
+
+
+def _check_tiny(c):
+    assert len(c["slots"]) == 1 and 0 < c["slots"][0] <= FLAG_PASS  # P < 64: one partial group
+
+
+def _check_tiny_behind(c):
+    assert c["slots"].tolist() == [0]  # num_slots = 0, no offsets produced
+
+
+SCENES = {"equal_splats": (equal_splats, _check_equal_splats), "mixed_splats": (mixed_splats, _check_mixed_splats),
+          "wall": (wall, _check_wall), "huge_gaussians": (huge_gaussians, _check_huge_gaussians),
+          "tiny": (tiny, _check_tiny), "tiny_behind": (tiny_behind, _check_tiny_behind)}
+
+
+def _assert_same_bits(a, b, what):
+    for k in Hh.GRAD_KEYS:
+        if k in a:
+            assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), f"{what}: {k}"
+
+
+def _three_ways(s, grads, name, st, ref, **tuning):
+    """Automatic mode (checked against the oracle), everything on one wave, the cooperative kernel; a repeat of the last."""
+    set_tuning(**tuning)
+    auto = Hh.hip_run(s, grads)
+    assert (auto["radii"] == st["radii"]).all(), f"{name}: radii"
+    Hh.assert_parity_strict(auto, st, ref, s, grads, context=name, nthreads=NT)
+    assert all(np.isfinite(v).all() for k, v in auto.items() if k.startswith("dL_"))
+    out = {"auto": auto}
+    for mode, heavy in (("one_wave", False), ("cooperative", True), ("cooperative_again", True)):
+        set_tuning(heavy_groups=heavy, **tuning)
+        out[mode] = Hh.hip_run(s, grads)
+        _assert_same_bits(auto, out[mode], f"{name}: automatic mode against {mode}")
+    set_tuning()
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_group_walk(name):
+    make, check = SCENES[name]
+    s = make()
+    grads = S.upstream_grads(90, s["W"], s["H"])
+    st = Hh.oracle_forward(s)
+    check(census(s, st))
+    ref = Hh.oracle_backward(s, st, grads)
+    P = s["means3D"].shape[0]
+    # stale memory would show in rows the kernel must write as exact zeros (the gradient tensors are torch.empty)
+    poison = [torch.full((max(P, 1024) * 16,), float("nan"), device="cuda") for _ in range(8)]
+    del poison
+    # 1. culling off: the lists, hence the slots and their flags, are the ones the census was taken from
+    set_tuning(tile_cull=False)
+    assert Hh.hip_run(s, keep_state=True)["num_rendered"] == st["num_rendered"]
+    out = _three_ways(s, grads, name + "/cull_off", st, ref, tile_cull=False)
+    if name == "wall":
+        for mode, got in out.items():
+            for k in Hh.GRAD_KEYS:
+                if k in got:
+                    assert not got[k][64:].any(), f"{mode}: {k}: groups without a written slot get exact zeros"
+            assert np.abs(got["dL_dmeans3D"][:64]).max() > 0
+    if name == "tiny_behind":
+        assert st["num_rendered"] == 0
+        for k in Hh.GRAD_KEYS:
+            if k in out["auto"]:
+                assert not out["auto"][k].any(), f"{k}: nothing rendered, exact zeros"
+    # 2. default tuning (culling on)
+    _three_ways(s, grads, name, st, ref)
+    set_tuning()
