@@ -7,5 +7,6 @@ name so that GScream's `gaussian_renderer/__init__.py:15` imports this build unc
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians,  # noqa: F401
                          set_tuning)
+from .metrics import evaluate_views, image_metrics  # noqa: F401  (test-view PSNR / SSIM: gscream_amd/metrics.py, INTEGRATION R)
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "set_tuning"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "set_tuning", "evaluate_views", "image_metrics"]

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "gsr_anchor_adjust_workspace_bytes", "gsr_anchor_adjust_offsets", "gsr_anchor_adjust_plan", "gsr_anchor_adjust_gather",
     "gsr_adam_step",
     "gsr_depth_points", "gsr_point_normals",
+    "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -195,6 +196,10 @@ def load():
     lib.gsr_depth_points.argtypes = [_c_int, _c_int] + [_vp] * 5
     lib.gsr_point_normals.restype = _c_int
     lib.gsr_point_normals.argtypes = [_c_int, _c_int, _vp, _c_int, _c_float, ctypes.c_double, _vp, _vp]
+    lib.gsr_image_metrics_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_image_metrics_workspace_bytes.argtypes = [_c_int] * 4
+    lib.gsr_image_metrics.restype = _c_int
+    lib.gsr_image_metrics.argtypes = [_c_int] * 4 + [_vp] * 3 + [ctypes.c_longlong] * 2 + [_c_int] + [_vp] * 4
     _lib = lib
     return lib
 

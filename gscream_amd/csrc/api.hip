@@ -4,6 +4,7 @@
 // kernels on the caller's stream and reports failures as an int code + thread-local message.
 // Orchestration replaces CudaRasterizer::Rasterizer::{forward,backward,visible_filter,
 // position2D_filter,markVisible} (DGR rasterizer_impl.cu:141-153,199-347,350-530,536-643).
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -1071,5 +1072,42 @@ extern "C" int gsr_point_normals(int H, int W, const float* points, int size, fl
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: size=%d (need an odd size, 1 .. 15)", size);
     if (!points || !normals) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: points or normals is NULL");
     GSR_HIP(normals_launch_fit(H, W, points, size, gamma, eps, normals, (hipStream_t)stream), "point normals");
+    return GSR_OK;
+}
+
+// ---- test-view metrics (metrics.hip) ----
+static int metrics_check_sizes(int B, int C, int H, int W)
+{
+    if (B <= 0 || C <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: B=%d C=%d (need both > 0)", B, C);
+    if ((int64_t)B * (int64_t)C > 65535)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: B=%d C=%d has too many planes (need B*C <= 65535)", B, C);
+    if (H < 3 || W < 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: H=%d W=%d (need both >= 3: reflect padding of 2)", H, W);
+    if ((double)C * (double)H * (double)W >= 2147483392.0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: C=%d H=%d W=%d has too many elements (need C*H*W < 2^31 - 256)", C, H, W);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_image_metrics_workspace_bytes(int B, int C, int H, int W)
+{
+    if (metrics_check_sizes(B, C, H, W)) return 0;
+    const size_t tiles = (size_t)((W + METRICS_TILE_W - 1) / METRICS_TILE_W) * (size_t)((H + METRICS_TILE_H - 1) / METRICS_TILE_H);
+    return (size_t)B * (size_t)C * tiles * 8 * sizeof(double);
+}
+
+extern "C" int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
+                                 long long mask_stride_c, int flags, void* workspace, double* sums, float* metrics, void* stream)
+{
+    if (int rc = metrics_check_sizes(B, C, H, W)) return rc;
+    if (!pred || !gt || !workspace || !sums || !metrics)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: pred, gt, workspace, sums or metrics is NULL");
+    if (flags & ~(GSR_METRICS_CLAMP | GSR_METRICS_QUANTIZE)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: unknown flag bits in %d", flags);
+    if (mask_stride_b < 0 || mask_stride_c < 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: negative mask stride (%lld, %lld)", mask_stride_b, mask_stride_c);
+    double taps[3], total = 0.0;  // g_k = exp(-(k-2)^2 / 4.5) / sum, k = 0 .. 4 (sigma 1.5), in fp64
+    for (int k = 0; k < 3; k++) taps[k] = exp(-(double)((k - 2) * (k - 2)) / 4.5);
+    total = ((taps[0] + taps[1]) + taps[2]) + (taps[1] + taps[0]);
+    for (int k = 0; k < 3; k++) taps[k] /= total;
+    GSR_HIP(metrics_launch(B, C, H, W, pred, gt, mask, mask_stride_b, mask_stride_c, flags, taps, workspace, sums, metrics, (hipStream_t)stream),
+            "image metrics");
     return GSR_OK;
 }

@@ -474,3 +474,11 @@ hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_
 // normals.hip: depth -> point map, point map -> per-pixel plane-fit normals (both validated by the caller)
 hipError_t normals_launch_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, hipStream_t stream);
 hipError_t normals_launch_fit(int H, int W, const float* points, int size, float gamma, double eps, float* normals, hipStream_t stream);
+
+// metrics.hip: per-image L1 / MSE / PSNR / 5x5 reflect-padded SSIM, plain and masked (validated by the caller).  One workgroup per
+// METRICS_TILE_H x METRICS_TILE_W tile of a plane writes eight fp64 partial sums: the workspace is B*C*tiles*8 doubles.
+#define METRICS_TILE_W 32
+#define METRICS_TILE_H 16
+hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
+                          long long mask_stride_c, int flags, const double taps[3] /* g_0, g_1, g_2 of the window */, void* workspace,
+                          double* sums, float* metrics, hipStream_t stream);

@@ -473,6 +473,52 @@ int gsr_point_normals(int H, int W, const float* points /* [3,H,W] */, int size,
                       void* stream /* hipStream_t */);
 
 /*
+ * Test-view metrics: what evaluate() (train.py:905-990) and training_report (train.py:655-708) log per view -- L1, MSE, PSNR
+ * (utils/image_utils.py:22-32) and my_ssim (utils/loss_utils.py:123-128) -- over the whole image and over a boolean mask, for a
+ * batch of images in one call.  pred and gt are fp32 [B,C,H,W]; mask is NULL or bytes (0 = false) read through
+ * mask + b*mask_stride_b + c*mask_stride_c + i*W + j, so mask_stride_c = 0 is a channel-broadcast mask (evaluate()'s expand) and
+ * mask_stride_b = 0 one mask for the whole batch.  H, W >= 3 is what reflect padding of 2 needs.
+ *
+ *   input transform, per element, fp32, one rounding per operation, no contraction:
+ *       flag CLAMP     x := min(max(x, 0), 1)                                  (training_report's torch.clamp; NaN stays NaN)
+ *       flag QUANTIZE  x := trunc(min(max(x*255 + 0.5, 0), 255)) / 255         (torchvision save_image, then to_tensor: evaluate()'s PNG round trip)
+ *                      applied to pred and gt alike; implies nothing else (with both flags: CLAMP, then QUANTIZE)
+ *   d      = x - y                                            fp32 (exact once widened)
+ *   window g_k = exp(-(k-2)^2 / 4.5) / sum_k(...)  k = 0..4, evaluated in fp64; w_ij = g_i g_j
+ *   pad    reflect without repeating the edge: index -1 -> 1, -2 -> 2, H -> H-2, H+1 -> H-3 (torch 'reflect', scipy 'mirror')
+ *   mu1 = w*x   mu2 = w*y   e11 = w*(x x)   e22 = w*(y y)   e12 = w*(x y)          fp64 (products of fp32 values are exact in fp64)
+ *   s1 = e11 - mu1^2   s2 = e22 - mu2^2   s12 = e12 - mu1 mu2
+ *   ssim  = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2) + 1e-12)      C1 = 1e-4, C2 = 9e-4
+ *   dssim = min(max((1 - ssim)/2, 0), 1)
+ *   per image b, over all C*H*W elements, and over the elements where the mask is true:
+ *       sums[b] = { n, sum|d|, sum d^2, sum dssim,  n_m, sum_m|d|, sum_m d^2, sum_m dssim }     fp64; n and n_m are exact integers
+ *       metrics[b] = { l1, mse, psnr, ssim, l1_m, mse_m, psnr_m, ssim_m }                        each formed in fp64, rounded to fp32 once
+ *       l1 = sum|d| / n     mse = sum d^2 / n     psnr = -10 log10(mse)     ssim = 1 - 2 (sum dssim / n)
+ *
+ * An empty mask gives NaN in the four masked entries (0/0, as torch.mean of an empty selection) and leaves the unmasked ones alone;
+ * mse == 0 gives psnr = +inf; a NaN pixel makes that image's affected entries NaN (the mask selects, it does not multiply: a NaN
+ * outside the mask reaches the masked entries only through the 5x5 windows that hold it) and touches no other image of the batch;
+ * without a mask the four masked entries equal the unmasked ones.  The window sums are separable (rows, then columns), every sum is
+ * taken in a fixed order without atomics: the same inputs give the same bits.
+ *
+ * The PSNR half is pinned by a run of the reference's utils/image_utils.py (tests/golden/ref_metrics.npz).  The SSIM half is NOT pinned
+ * by a reference run: the expression is kornia 0.6.12's metrics.ssim(img1, img2, 5, 1.0, 1e-12, 'same') with filter2d's default reflect
+ * border, as utils/my_ssim.py calls it, written down from its source; the reference evaluates it (and E[x^2] - mu^2 in it) in fp32,
+ * this call in fp64, and returns the value the expression defines (INTEGRATION R has the measured gap).
+ *
+ * workspace: gsr_image_metrics_workspace_bytes(B, C, H, W) bytes (0 for sizes the call rejects), written before it is read.  The call
+ * launches on `stream`, never synchronises and reads nothing back.  Rejected before launching (GSR_ERR_INVALID_ARGUMENT, text in
+ * gsr_last_error): NULL pred, gt, workspace, sums or metrics; B or C <= 0 or B*C > 65535; H or W < 3; C*H*W >= 2^31 - 256; unknown
+ * flag bits; negative mask strides.
+ */
+#define GSR_METRICS_CLAMP    1
+#define GSR_METRICS_QUANTIZE 2
+size_t gsr_image_metrics_workspace_bytes(int B, int C, int H, int W);
+int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt,
+                      const uint8_t* mask /* or NULL */, long long mask_stride_b, long long mask_stride_c,
+                      int flags, void* workspace, double* sums /* [B,8] */, float* metrics /* [B,8] */, void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
