@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "gsr_adam_step",
     "gsr_depth_points", "gsr_point_normals",
     "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
+    "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -63,6 +64,17 @@ class AdamTensor(ctypes.Structure):
 
 
 ADAM_MAX_TENSORS = 32
+
+
+class FramePanel(ctypes.Structure):
+    """gsr_frame_panel: one panel of gsr_frame_compose's table (device pointers, signed strides in elements, output columns, FRAME_* mode)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src2", ctypes.c_void_p), ("lut", ctypes.c_void_p), ("stride_b", ctypes.c_longlong),
+                ("stride_c", ctypes.c_longlong), ("stride_y", ctypes.c_longlong), ("stride_x", ctypes.c_longlong), ("x0", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("mode", ctypes.c_int32)]
+
+
+FRAME_MAX_PANELS = 8
+FRAME_QUANT, FRAME_QUANT_CLAMP, FRAME_ABSDIFF, FRAME_NORMAL, FRAME_CMAP_CV, FRAME_CMAP_MPL_ALIGNED, FRAME_CMAP_MPL = range(7)
 
 
 class Profile(ctypes.Structure):
@@ -200,6 +212,12 @@ def load():
     lib.gsr_image_metrics_workspace_bytes.argtypes = [_c_int] * 4
     lib.gsr_image_metrics.restype = _c_int
     lib.gsr_image_metrics.argtypes = [_c_int] * 4 + [_vp] * 3 + [ctypes.c_longlong] * 2 + [_c_int] + [_vp] * 4
+    lib.gsr_frame_stats_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_frame_stats_workspace_bytes.argtypes = [_c_int] * 3
+    lib.gsr_frame_stats.restype = _c_int
+    lib.gsr_frame_stats.argtypes = [_c_int] * 3 + [_vp] * 7
+    lib.gsr_frame_compose.restype = _c_int
+    lib.gsr_frame_compose.argtypes = [_c_int] * 5 + [ctypes.POINTER(FramePanel)] + [_vp] * 3
     _lib = lib
     return lib
 

@@ -1111,3 +1111,70 @@ extern "C" int gsr_image_metrics(int B, int C, int H, int W, const float* pred, 
             "image metrics");
     return GSR_OK;
 }
+
+// ---- render_set's output frames (frames.hip) ----
+static int frames_check_sizes(const char* what, int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: B=%d H=%d W=%d (need all > 0)", what, B, H, W);
+    if (B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: B=%d has too many frames (need B <= 65535)", what, B);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL / 4)  // (H*W*4 itself can pass 2^63)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d has too many pixels (need H*W*4 < 2^31 - 256)", what, H, W);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_frame_stats_workspace_bytes(int B, int H, int W)
+{
+    if (frames_check_sizes("frame stats", B, H, W)) return 0;
+    const size_t chunks = ((size_t)H * (size_t)W + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK;
+    return (size_t)B * chunks * 8 * sizeof(double);
+}
+
+extern "C" int gsr_frame_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
+                               double* stats, float* params, void* stream)
+{
+    if (int rc = frames_check_sizes("frame stats", B, H, W)) return rc;
+    if (!depth || !workspace || !stats || !params)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame stats: depth, workspace, stats or params is NULL");
+    if (lsq_mask && !target) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame stats: an lsq_mask needs a target, which is NULL");
+    GSR_HIP(frames_launch_stats(B, H, W, depth, target, lsq_mask, workspace, stats, params, (hipStream_t)stream), "frame stats");
+    return GSR_OK;
+}
+
+extern "C" int gsr_frame_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
+                                 uint8_t* out, void* stream)
+{
+    if (int rc = frames_check_sizes("frame compose", B, H, W_out)) return rc;
+    if (channels_out != 3 && channels_out != 4)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: channels_out=%d (need 3 or 4)", channels_out);
+    if (n < 1 || n > GSR_FRAME_MAX_PANELS)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: n=%d panels (need 1 .. %d)", n, GSR_FRAME_MAX_PANELS);
+    if (!panels || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panels or out is NULL");
+    int order[GSR_FRAME_MAX_PANELS];
+    for (int j = 0; j < n; j++) {
+        const gsr_frame_panel& p = panels[j];
+        if (p.mode < GSR_FRAME_QUANT || p.mode > GSR_FRAME_CMAP_MPL)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has the unknown mode %d", j, p.mode);
+        if (!p.src) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has a NULL src", j);
+        if (p.mode == GSR_FRAME_ABSDIFF && !p.src2) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d is ABSDIFF with a NULL src2", j);
+        if (p.mode >= GSR_FRAME_CMAP_CV && (!p.lut || !params))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has a CMAP mode with a NULL lut or params", j);
+        if (p.width <= 0 || p.x0 < 0 || (int64_t)p.x0 + (int64_t)p.width > (int64_t)W_out)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d covers columns [%d, %lld), outside [0, %d) or empty", j, p.x0,
+                            (long long)p.x0 + (long long)p.width, W_out);
+        int k = j;  // insertion by x0
+        for (; k > 0 && panels[order[k - 1]].x0 > p.x0; k--) order[k] = order[k - 1];
+        order[k] = j;
+    }
+    int next = 0;
+    for (int k = 0; k < n; k++) {
+        const gsr_frame_panel& p = panels[order[k]];
+        if (p.x0 != next)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d starts at column %d where %d is next (the panels %s)", order[k], p.x0,
+                            next, p.x0 < next ? "overlap" : "leave a gap");
+        next = p.x0 + p.width;
+    }
+    if (next != W_out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: the panels end at column %d of %d (they leave a gap)", next, W_out);
+    const bool dwords = ((uintptr_t)out & 3) == 0 && (channels_out == 4 || W_out % 4 == 0);
+    GSR_HIP(frames_launch_compose(B, H, W_out, channels_out, n, panels, params, out, dwords, (hipStream_t)stream), "frame compose");
+    return GSR_OK;
+}

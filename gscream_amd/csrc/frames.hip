@@ -1,0 +1,335 @@
+// frames.hip -- what render_set (train.py:710-848) does between the render and the PNG encoder, as finished uint8 pictures on the
+// device: save_image's quantisation, the error map, the normal picture's second normalisation, compute_scale_and_shift (:198-218),
+// the two colour maps (cv2.applyColorMap, plt.imsave), the flips, the one-channel expand and the concat.  The rules are in
+// include/gsraster.h in full.
+//
+// The reference does this per frame in eager torch and on the host: a min, a max, four fp32 .cpu() copies (22.9 MB at 567 x 1008 for a
+// 6.9 MB file), numpy and cv2 on the CPU, five masked sums with a nonzero (a host stop) and matplotlib for the depth panel.  Here:
+//   stats    : partial -- one workgroup per FRAME_STATS_CHUNK = 4096 elements of a frame reads depth (and target, mask) once and
+//              writes eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}, reduced in a fixed order (a thread's elements in
+//              order, xor-butterfly over the wave, the four waves in order); finish -- one workgroup per frame reduces the frame's
+//              partials the same way and writes stats[b] and params[b].  With a target both run a second time for lo2 / hi2 of the
+//              [aligned | target] panel, reading scale and shift from params[b] on the device.
+//   compose  : one thread makes four consecutive output pixels of one row.  The panel table travels in the kernel arguments; the
+//              loop over panels is uniform (scalar loads of the table), a lane takes part in the panels its pixels lie in, so a wave
+//              diverges only where it straddles a panel edge.  Sources are read through signed strides (flip, expand, interleaved
+//              normals); stores are whole dwords (three for 4 RGB pixels, one per RGBA pixel) or bytes, a template argument.
+// No atomics, nothing read back, the same bits for the same inputs.  Both are bound by memory traffic: 4 .. 12 bytes read and 3 .. 4
+// written per output pixel.
+//
+// Arithmetic: every fp32 operation below rounds once (contraction is off from the pragma on; min / max are comparisons, so a NaN
+// stays where the rules keep it), `/` is the IEEE division and sqrtf the correctly rounded root, as in adam.hip.  fp32 denormals are
+// kept (the default kernel mode).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gsr_common.h"
+
+#pragma clang fp contract(off)
+
+#define FRM_THREADS 256
+static_assert(FRAME_STATS_CHUNK % FRM_THREADS == 0, "every thread of a full chunk reads the same number of elements");
+static_assert(sizeof(gsr_frame_panel) == 72, "gsr_frame_panel is 3 pointers, 4 strides and 3 ints (padded to 8 bytes)");
+
+struct FrmTable {
+    gsr_frame_panel p[GSR_FRAME_MAX_PANELS];
+    int32_t n;
+};
+static_assert(sizeof(FrmTable) <= 1024, "the table travels in the kernel arguments");
+
+// ---- stats ----
+// slots 0 .. 4 and 7 add, 5 takes the minimum, 6 the maximum (never NaN: the comparisons that fill them reject it)
+__device__ __forceinline__ double frm_join(int q, double a, double b)
+{
+    if (q == 5) return b < a ? b : a;
+    if (q == 6) return b > a ? b : a;
+    return a + b;
+}
+
+// over the wave by xor-butterfly (a fixed tree), then over the waves in order; the result is valid in thread 0
+__device__ __forceinline__ void frm_block_join8(double (&v)[8], double* red /* [FRM_THREADS/64][8] */)
+{
+#pragma unroll
+    for (int q = 0; q < 8; q++)
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) v[q] = frm_join(q, v[q], __shfl_xor(v[q], s, 64));
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int q = 0; q < 8; q++) red[wave * 8 + q] = v[q];
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            double s = red[q];
+            for (int w = 1; w < FRM_THREADS / 64; w++) s = frm_join(q, s, red[w * 8 + q]);
+            v[q] = s;
+        }
+}
+
+__device__ __forceinline__ void frm_extrema(float x, double (&acc)[8])
+{
+    const double v = (double)x;
+    acc[5] = v < acc[5] ? v : acc[5];
+    acc[6] = v > acc[6] ? v : acc[6];
+    acc[7] += x != x ? 1.0 : 0.0;
+}
+
+#define FRM_ACC_INIT {0.0, 0.0, 0.0, 0.0, 0.0, __builtin_huge_val(), -__builtin_huge_val(), 0.0}
+
+// PASS 1: the five sums and the extrema of depth.  PASS 2: the extrema of [depth*scale + shift | target], scale / shift from params.
+template <int PASS>
+__global__ void __launch_bounds__(FRM_THREADS) frame_stats_partial_kernel(int HW, const float* __restrict__ depth, const float* __restrict__ target,
+                                                                          const float* __restrict__ mask, const float* __restrict__ params,
+                                                                          double* __restrict__ partials)
+{
+    __shared__ double red[(FRM_THREADS / 64) * 8];
+    const int b = (int)blockIdx.y;
+    const size_t base = (size_t)b * (size_t)HW;
+    const int start = (int)blockIdx.x * FRAME_STATS_CHUNK;  // < HW < 2^29
+    const int end = min(start + FRAME_STATS_CHUNK, HW);
+    float scale = 0.0f, shift = 0.0f;
+    if (PASS == 2) {
+        scale = params[(size_t)b * 8 + 2];
+        shift = params[(size_t)b * 8 + 3];
+    }
+    double acc[8] = FRM_ACC_INIT;
+    for (int i = start + (int)threadIdx.x; i < end; i += FRM_THREADS) {
+        const float d = depth[base + (size_t)i];
+        if (PASS == 1) {
+            frm_extrema(d, acc);
+            if (target) {
+                const float y = target[base + (size_t)i];
+                const float m = mask ? mask[base + (size_t)i] : 1.0f;
+                const double dd = (double)d, md = (double)m * dd;  // (exact)
+                acc[0] += md * dd;
+                acc[1] += md;
+                acc[2] += (double)m;
+                acc[3] += md * (double)y;
+                acc[4] += (double)m * (double)y;
+            }
+        } else {
+            float a = d * scale;
+            a = a + shift;
+            frm_extrema(a, acc);
+            frm_extrema(target[base + (size_t)i], acc);
+        }
+    }
+    frm_block_join8(acc, red);
+    if (threadIdx.x == 0) {
+        double* out = partials + ((size_t)b * (size_t)gridDim.x + (size_t)blockIdx.x) * 8;
+#pragma unroll
+        for (int q = 0; q < 8; q++) out[q] = acc[q];
+    }
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(FRM_THREADS) frame_stats_finish_kernel(int chunks, const double* __restrict__ partials, double* __restrict__ stats,
+                                                                         float* __restrict__ params)
+{
+    __shared__ double red[(FRM_THREADS / 64) * 8];
+    const int b = (int)blockIdx.x;
+    const double* in = partials + (size_t)b * (size_t)chunks * 8;
+    double acc[8] = FRM_ACC_INIT;
+    for (int i = threadIdx.x; i < chunks; i += FRM_THREADS)
+#pragma unroll
+        for (int q = 0; q < 8; q++) acc[q] = frm_join(q, acc[q], in[(size_t)i * 8 + q]);
+    frm_block_join8(acc, red);
+    if (threadIdx.x != 0) return;
+    const float nan = __builtin_nanf("");
+    const float lo = acc[7] > 0.0 ? nan : (float)acc[5], hi = acc[7] > 0.0 ? nan : (float)acc[6];  // (fp32 values: the casts are exact)
+    float* p = params + (size_t)b * 8;
+    if (PASS == 2) {
+        p[4] = lo;
+        p[5] = hi;
+        return;
+    }
+    const double a00 = acc[0], a01 = acc[1], a11 = acc[2], b0 = acc[3], b1 = acc[4];
+    const double det = a00 * a11 - a01 * a01;
+    double x0 = 0.0, x1 = 0.0;
+    if (det != 0.0) {  // (a NaN determinant is "nonzero", as in the reference: the quotients are NaN)
+        x0 = (a11 * b0 - a01 * b1) / det;
+        x1 = (-a01 * b0 + a00 * b1) / det;
+    }
+    double* s = stats + (size_t)b * 8;
+    s[0] = a00;
+    s[1] = a01;
+    s[2] = a11;
+    s[3] = b0;
+    s[4] = b1;
+    s[5] = det;
+    s[6] = x0;
+    s[7] = x1;
+    p[0] = lo;
+    p[1] = hi;
+    p[2] = fabsf((float)x0);
+    p[3] = (float)x1;
+    p[4] = p[5] = p[6] = p[7] = 0.0f;
+}
+
+hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
+                               double* stats, float* params, hipStream_t stream)
+{
+    const int HW = H * W;  // < 2^29
+    const int chunks = (HW + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK;
+    double* partials = (double*)workspace;
+    const dim3 grid((uint32_t)chunks, (uint32_t)B);
+    hipLaunchKernelGGL(frame_stats_partial_kernel<1>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, lsq_mask, (const float*)nullptr, partials);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(frame_stats_finish_kernel<1>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
+    e = hipGetLastError();
+    if (e != hipSuccess || !target) return e;
+    hipLaunchKernelGGL(frame_stats_partial_kernel<2>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, (const float*)nullptr, (const float*)params,
+                       partials);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(frame_stats_finish_kernel<2>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
+    return hipGetLastError();
+}
+
+// ---- compose ----
+__device__ __forceinline__ float frm_clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }  // NaN fails both comparisons and stays
+
+// trunc(min(max(v, 0), 255)) as an integer, NaN -> 0
+__device__ __forceinline__ uint32_t frm_byte(float v)
+{
+    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+    return v == v ? (uint32_t)(int)v : 0u;
+}
+
+__device__ __forceinline__ uint32_t frm_quantise(float x)
+{
+    float v = x * 255.0f;
+    v = v + 0.5f;
+    return frm_byte(v);
+}
+
+__device__ __forceinline__ uint32_t frm_rgba(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return r | (g << 8) | (b << 16) | (a << 24); }
+
+__device__ __forceinline__ uint32_t frm_lut(const uint8_t* __restrict__ lut, uint32_t i)
+{
+    return frm_rgba(lut[i * 3], lut[i * 3 + 1], lut[i * 3 + 2], 255u);
+}
+
+__device__ __forceinline__ uint32_t frm_map_mpl(float v, float lo, float hi, const uint8_t* __restrict__ lut)
+{
+    if (lo != lo || hi != hi) return 0u;
+    if (hi == lo) return frm_lut(lut, 0u);
+    const float den = (float)((double)hi - (double)lo);
+    float t = (v - lo) / den;
+    t = t * 256.0f;
+    if (t != t) return 0u;
+    t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);  // (int) trunc(t) clipped to 0 .. 255
+    return frm_lut(lut, (uint32_t)(int)t);
+}
+
+// one output pixel as r | g << 8 | b << 16 | a << 24.  p is uniform over the wave; lx is the column inside the panel.
+__device__ __forceinline__ uint32_t frm_pixel(const gsr_frame_panel& p, const float* __restrict__ pr, int b, int y, int lx)
+{
+    const long long at = (long long)b * p.stride_b + (long long)y * p.stride_y + (long long)lx * p.stride_x;
+    const float* s = p.src + at;
+    const long long sc = p.stride_c;
+    switch (p.mode) {
+    case GSR_FRAME_QUANT:
+        return frm_rgba(frm_quantise(s[0]), frm_quantise(s[sc]), frm_quantise(s[2 * sc]), 255u);
+    case GSR_FRAME_QUANT_CLAMP:
+        return frm_rgba(frm_quantise(frm_clamp01(s[0])), frm_quantise(frm_clamp01(s[sc])), frm_quantise(frm_clamp01(s[2 * sc])), 255u);
+    case GSR_FRAME_ABSDIFF: {
+        const float* s2 = p.src2 + at;
+        return frm_rgba(frm_quantise(fabsf(frm_clamp01(s[0]) - s2[0])), frm_quantise(fabsf(frm_clamp01(s[sc]) - s2[sc])),
+                        frm_quantise(fabsf(frm_clamp01(s[2 * sc]) - s2[2 * sc])), 255u);
+    }
+    case GSR_FRAME_NORMAL: {
+        const float x = s[0], yv = s[sc], z = s[2 * sc];
+        float q = x * x;
+        const float yy = yv * yv, zz = z * z;
+        q = q + yy;
+        q = q + zz;
+        float r = sqrtf(q);
+        r = r < 1e-12f ? 1e-12f : r;  // max(r, 1e-12) that keeps a NaN
+        float c[3] = {x / r, yv / r, z / r};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            c[k] = c[k] + 1.0f;
+            c[k] = c[k] / 2.0f;
+        }
+        return frm_rgba(frm_quantise(c[0]), frm_quantise(c[1]), frm_quantise(c[2]), 255u);
+    }
+    case GSR_FRAME_CMAP_CV: {
+        const float lo = pr[0], hi = pr[1];
+        uint32_t i = 0u;
+        if (hi != lo && fabsf(lo) <= 3.402823466e38f && fabsf(hi) <= 3.402823466e38f) {  // both finite (a NaN fails the comparison)
+            const float num = s[0] - lo, den = hi - lo;
+            float t = num / den;
+            t = 255.0f * t;
+            i = frm_byte(t);
+        }
+        return frm_lut(p.lut, i);
+    }
+    case GSR_FRAME_CMAP_MPL_ALIGNED: {
+        float v = s[0] * pr[2];
+        v = v + pr[3];
+        return frm_map_mpl(v, pr[4], pr[5], p.lut);
+    }
+    default:  // GSR_FRAME_CMAP_MPL (the caller has rejected every other value)
+        return frm_map_mpl(s[0], pr[4], pr[5], p.lut);
+    }
+}
+
+template <int CH, bool DWORDS>
+__global__ void __launch_bounds__(FRM_THREADS) frame_compose_kernel(int H, int W_out, int quads /* ceil(W_out / 4) */, FrmTable tab,
+                                                                    const float* __restrict__ params, uint8_t* __restrict__ out)
+{
+    const int t = (int)blockIdx.x * FRM_THREADS + (int)threadIdx.x;  // H * quads <= H * W_out < 2^29
+    if (t >= H * quads) return;
+    const int b = (int)blockIdx.y;
+    const int y = t / quads, x = (t - y * quads) * 4;
+    const int count = min(4, W_out - x);
+    const float* pr = params ? params + (size_t)b * 8 : nullptr;  // (NULL only when no panel reads it)
+    uint32_t px[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < tab.n; j++) {  // uniform: the table is read with scalar loads (checked in the gfx950 ISA: s_load from the kernel
+                                       // arguments at a runtime offset, no scratch)
+        const gsr_frame_panel& p = tab.p[j];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int lx = x + k - p.x0;
+            if (k < count && lx >= 0 && lx < p.width) px[k] = frm_pixel(p, pr, b, y, lx);
+        }
+    }
+    uint8_t* o = out + (((size_t)b * (size_t)H + (size_t)y) * (size_t)W_out + (size_t)x) * CH;
+    if (DWORDS && CH == 4) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < count) ((uint32_t*)o)[k] = px[k];
+    } else if (DWORDS) {  // CH == 3 and W_out % 4 == 0: count == 4, and o is a multiple of 12 bytes past the aligned base
+        uint32_t* o32 = (uint32_t*)o;
+        o32[0] = (px[0] & 0xffffffu) | (px[1] << 24);
+        o32[1] = ((px[1] >> 8) & 0xffffu) | (px[2] << 16);
+        o32[2] = ((px[2] >> 16) & 0xffu) | (px[3] << 8);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < count)
+#pragma unroll
+                for (int c = 0; c < CH; c++) o[k * CH + c] = (uint8_t)(px[k] >> (8 * c));
+    }
+}
+
+hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
+                                 uint8_t* out, bool dwords, hipStream_t stream)
+{
+    FrmTable tab = {};
+    for (int j = 0; j < n; j++) tab.p[j] = panels[j];
+    tab.n = n;
+    const int quads = (W_out + 3) / 4;
+    const dim3 grid((uint32_t)(((long long)H * quads + FRM_THREADS - 1) / FRM_THREADS), (uint32_t)B), block(FRM_THREADS);
+    if (channels_out == 4) {
+        if (dwords) hipLaunchKernelGGL((frame_compose_kernel<4, true>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
+        else hipLaunchKernelGGL((frame_compose_kernel<4, false>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
+    } else {
+        if (dwords) hipLaunchKernelGGL((frame_compose_kernel<3, true>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
+        else hipLaunchKernelGGL((frame_compose_kernel<3, false>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
+    }
+    return hipGetLastError();
+}

@@ -482,3 +482,12 @@ hipError_t normals_launch_fit(int H, int W, const float* points, int size, float
 hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
                           long long mask_stride_c, int flags, const double taps[3] /* g_0, g_1, g_2 of the window */, void* workspace,
                           double* sums, float* metrics, hipStream_t stream);
+
+// frames.hip: render_set's output frames (validated by the caller).  Stats: one workgroup per FRAME_STATS_CHUNK elements of a frame writes
+// eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}: the workspace is B*chunks*8 doubles, used again by the second pass (lo2 / hi2).
+// Compose: `dwords` = whole-dword stores (the caller has checked out's alignment and channels_out == 4 or W_out % 4 == 0).
+#define FRAME_STATS_CHUNK 4096
+hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
+                               double* stats, float* params, hipStream_t stream);
+hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
+                                 uint8_t* out, bool dwords, hipStream_t stream);

@@ -519,6 +519,84 @@ int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float
                       int flags, void* workspace, double* sums /* [B,8] */, float* metrics /* [B,8] */, void* stream /* hipStream_t */);
 
 /*
+ * Output frames: what render_set (train.py:710-848) does between the render and the PNG encoder -- save_image's quantisation, the
+ * error map, the normal picture's second normalisation, the least-squares depth alignment of compute_scale_and_shift (:198-218), the
+ * two colour maps (cv2.applyColorMap for the spiral video, plt.imsave for the train / test sets), the flips, the one-channel expand
+ * and the concat -- as finished uint8 pictures on the device, in HWC order.  Everything per pixel is fp32 with one rounding per
+ * operation, nothing contracts into an FMA, division and sqrt are the correctly rounded ones; every rule ends in an integer:
+ *
+ *   quantise   q(x) = (uint8) trunc(min(max(x*255 + 0.5, 0), 255))          torchvision save_image's mul(255).add_(0.5).clamp_(0, 255).to(uint8):
+ *              the expression of GSR_METRICS_QUANTIZE.  NaN -> 0: the reference's float -> uint8 conversion of a NaN is unspecified
+ *              (it depends on the host), this is a choice.  -0.0 -> 0, +inf -> 255, -inf -> 0.
+ *              clamp, where a mode says so, comes first: x := min(max(x, 0), 1), a NaN stays  (render_set's torch.clamp, :766, :771)
+ *   abs-diff   e = |clamp(a) - b|, then q(e)                                 the error map, :794
+ *   normal     s = (x*x + y*y) + z*z;  r = max(sqrt(s), 1e-12f) (a NaN stays);  c = (v/r + 1) / 2 per component, then q(c)      :823-824
+ *   stats      per frame b over its H*W depths d:  lo = min d, hi = max d (a NaN anywhere makes both NaN).  With a target y and an lsq
+ *              mask m (fp32, NULL = ones), in fp64, the products m d and m y exact, m d d and m d y rounded once, each sum in a fixed order:
+ *                  a00 = sum m d d   a01 = sum m d   a11 = sum m   b0 = sum m d y   b1 = sum m y
+ *                  det = a00 a11 - a01 a01;   det == 0 -> x0 = x1 = 0,  else  x0 = (a11 b0 - a01 b1) / det,  x1 = (-a01 b0 + a00 b1) / det
+ *              (each product, difference and quotient one fp64 rounding), scale = |(float) x0|, shift = (float) x1.  The mask multiplies
+ *              (as the reference's does): a NaN depth under m = 0 still makes the sums NaN.  Then, in a second pass over the frame,
+ *              lo2 / hi2 = min / max over the 2 H W values of the panel [aligned | y], aligned = d*scale + shift (two fp32 roundings);
+ *              a NaN anywhere in it makes both NaN.  Without a target the five sums, scale, shift, lo2 and hi2 are 0.
+ *   CV map     t = (d - lo) / (hi - lo);  i = trunc(min(max(255 t, 0), 255)), NaN -> 0;  RGB = lut[i]          :807-810
+ *              hi == lo, or lo or hi not finite -> i = 0 for every pixel (the reference divides 0 by 0 there and converts the NaN
+ *              to uint8, which is unspecified: a choice).  With lo / hi the frame's own extrema 255 t lies in [0, 255] without the clamp.
+ *   MPL map    v = the value (the target half) or d*scale + shift (the aligned half);  den = (float)((double) hi2 - (double) lo2);
+ *              t = (v - lo2) / den;  i = min(max((int) trunc(t * 256), 0), 255);  RGBA = (lut[i], 255)           plt.imsave, :789
+ *              hi2 == lo2 -> i = 0;  lo2 or hi2 NaN -> every pixel (0, 0, 0, 0);  a pixel whose t is NaN -> (0, 0, 0, 0).  Pinned by
+ *              matplotlib's imsave on finite panels, a constant one and one with a NaN (tests/golden/ref_frames.npz); panels with
+ *              infinities are not pinned.
+ *
+ * gsr_frame_stats: depth, target (or NULL), lsq_mask (or NULL; needs a target) are fp32 [B,H,W].  Block partials (one workgroup per
+ * 4096 elements of a frame, eight doubles each), then one workgroup per frame sums them in a fixed order; with a target the same
+ * again for lo2 / hi2 once scale and shift exist (they are not derived from lo, hi and the sign of scale: the rounded products
+ * decide).  stats[b] = {a00, a01, a11, b0, b1, det, x0, x1} (fp64), params[b] = {lo, hi, scale, shift, lo2, hi2, 0, 0} (fp32).
+ * workspace: gsr_frame_stats_workspace_bytes(B, H, W) bytes (0 for sizes the call rejects), written before it is read.
+ *
+ * gsr_frame_compose: writes out[B, H, W_out, channels_out] uint8 from `n` panels, a HOST array that travels in the kernel arguments.
+ * Panel k covers the output columns [x0, x0 + width) of every row and reads, for output pixel (b, i, x0 + j) and channel c,
+ *     src[b*stride_b + c*stride_c + i*stride_y + j*stride_x]      (fp32 elements, signed strides; src2 through the same strides)
+ * so a horizontal flip is stride_x = -1 with src at the row's last element, a one-channel expand is stride_c = 0, and the [H*W, 3]
+ * normals of gsr_point_normals are stride_c = 1, stride_x = 3, stride_y = 3 W: nothing is materialised.  The modes:
+ *     QUANT              q(src), three channels                      QUANT_CLAMP   q(clamp(src))
+ *     ABSDIFF            q(|clamp(src) - src2|)                      NORMAL        the normal rule on src's three channels
+ *     CMAP_CV            the CV map of src (one channel: stride_c is not used) with params[b].lo / hi and lut
+ *     CMAP_MPL_ALIGNED   the MPL map of src*scale + shift            CMAP_MPL      the MPL map of src; both with params[b].lo2 / hi2 and lut
+ * lut is a device uint8 [256,3] (RGB).  channels_out = 4 adds alpha: 255, or the MPL map's; channels_out = 3 drops it.  params is
+ * [B,8] fp32 as gsr_frame_stats writes it and may be NULL when no panel has a CMAP mode.  The panels must tile [0, W_out) exactly,
+ * in any order.  One thread makes four consecutive output pixels of one row; they are stored as whole dwords when out is 4-byte
+ * aligned and channels_out = 4 or W_out % 4 == 0, else byte by byte (decided per call on the host).
+ *
+ * Both calls launch on `stream`, never synchronise, read nothing back, use no atomics and give the same bits for the same inputs.
+ * Rejected before launching (GSR_ERR_INVALID_ARGUMENT, text in gsr_last_error): NULL pointers (depth, workspace, stats, params; a mask
+ * without a target; panels, out, a panel's src, src2 for ABSDIFF, lut and params for the CMAP modes); B, H, W, W_out or a panel's width
+ * <= 0; B > 65535; H*W*4 (H*W_out*4) >= 2^31 - 256; channels_out other than 3 or 4; n outside 1 .. GSR_FRAME_MAX_PANELS; unknown
+ * modes; panels that overlap, leave a gap or leave [0, W_out).
+ */
+#define GSR_FRAME_MAX_PANELS 8
+#define GSR_FRAME_QUANT            0
+#define GSR_FRAME_QUANT_CLAMP      1
+#define GSR_FRAME_ABSDIFF          2
+#define GSR_FRAME_NORMAL           3
+#define GSR_FRAME_CMAP_CV          4
+#define GSR_FRAME_CMAP_MPL_ALIGNED 5
+#define GSR_FRAME_CMAP_MPL         6
+typedef struct {
+    const float* src;   /* device */
+    const float* src2;  /* device; ABSDIFF only, read through src's strides */
+    const uint8_t* lut; /* device [256,3]; the CMAP modes only */
+    long long stride_b, stride_c, stride_y, stride_x; /* elements, signed */
+    int32_t x0, width;  /* output columns [x0, x0 + width) */
+    int32_t mode;       /* GSR_FRAME_* */
+} gsr_frame_panel;
+size_t gsr_frame_stats_workspace_bytes(int B, int H, int W);
+int gsr_frame_stats(int B, int H, int W, const float* depth, const float* target /* or NULL */, const float* lsq_mask /* or NULL */,
+                    void* workspace, double* stats /* [B,8] */, float* params /* [B,8] */, void* stream /* hipStream_t */);
+int gsr_frame_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels /* host */,
+                      const float* params /* [B,8] or NULL */, uint8_t* out /* [B,H,W_out,channels_out] */, void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
