@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = (
     "gsr_depth_points", "gsr_point_normals",
     "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
     "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
+    "gsr_sort_block_keys", "gsr_sort_keys_workspace_bytes", "gsr_sort_keys_u64", "gsr_voxelize_workspace_bytes", "gsr_voxelize",
+    "gsr_kth_smallest_workspace_bytes", "gsr_kth_smallest_f32", "gsr_scene_init_fill",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -218,6 +220,19 @@ def load():
     lib.gsr_frame_stats.argtypes = [_c_int] * 3 + [_vp] * 7
     lib.gsr_frame_compose.restype = _c_int
     lib.gsr_frame_compose.argtypes = [_c_int] * 5 + [ctypes.POINTER(FramePanel)] + [_vp] * 3
+    lib.gsr_sort_block_keys.restype = _c_int
+    lib.gsr_sort_block_keys.argtypes = []
+    for name in ("gsr_sort_keys_workspace_bytes", "gsr_voxelize_workspace_bytes", "gsr_kth_smallest_workspace_bytes"):
+        getattr(lib, name).restype = ctypes.c_size_t
+        getattr(lib, name).argtypes = [_c_int]
+    lib.gsr_sort_keys_u64.restype = _c_int
+    lib.gsr_sort_keys_u64.argtypes = [_c_int] + [_vp] * 4
+    lib.gsr_voxelize.restype = _c_int
+    lib.gsr_voxelize.argtypes = [_c_int, _c_int, _vp, ctypes.c_double] + [_vp] * 5
+    lib.gsr_kth_smallest_f32.restype = _c_int
+    lib.gsr_kth_smallest_f32.argtypes = [_c_int, _c_int] + [_vp] * 4
+    lib.gsr_scene_init_fill.restype = _c_int
+    lib.gsr_scene_init_fill.argtypes = [_c_int] * 3 + [_vp, _vp, _c_float] + [_vp] * 9
     _lib = lib
     return lib
 

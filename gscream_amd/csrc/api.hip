@@ -724,6 +724,62 @@ extern "C" int gsr_knn_mean_dist2(int P, const float* points, float* mean_dist2,
     return GSR_OK;
 }
 
+// ---- scene initialisation (scene_init.hip) ----
+#define GSI_MAX_N (1 << 30)
+extern "C" int gsr_sort_block_keys(void) { return GSR_SORT_BLOCK_KEYS; }
+
+extern "C" size_t gsr_sort_keys_workspace_bytes(int N) { return N < 0 || N > GSI_MAX_N ? 0 : gsi_sort_workspace_bytes(N); }
+
+extern "C" int gsr_sort_keys_u64(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, void* stream)
+{
+    if (N < 0 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "sort keys: N=%d (need 0 <= N <= 2^30)", N);
+    if (N == 0) return GSR_OK;
+    if (!keys_in || !keys_out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "sort keys: keys_in, keys_out or workspace is NULL");
+    GSR_HIP(gsi_sort_launch(N, keys_in, keys_out, workspace, (hipStream_t)stream), "sort keys");
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_voxelize_workspace_bytes(int N) { return N < 0 || N > GSI_MAX_N ? 0 : gsi_voxelize_workspace_bytes(N); }
+
+extern "C" int gsr_voxelize(int N, int fp64, const void* points, double voxel_size, const float* voxel_size_dev, void* workspace, void* out,
+                            int32_t* info, void* stream)
+{
+    if (N < 0 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: N=%d (need 0 <= N <= 2^30)", N);
+    if (fp64 != 0 && fp64 != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: fp64=%d (need 0 or 1)", fp64);
+    if (!info || (N > 0 && (!points || !workspace || !out)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: points, workspace, out or info is NULL");
+    GSR_HIP(gsi_voxelize_launch(N, fp64, points, voxel_size, voxel_size_dev, workspace, out, info, (hipStream_t)stream), "voxelize");
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_kth_smallest_workspace_bytes(int N) { return N < 1 || N > GSI_MAX_N ? 0 : gsi_kth_workspace_bytes(N); }
+
+extern "C" int gsr_kth_smallest_f32(int N, int k, const float* values, void* workspace, float* out, void* stream)
+{
+    if (N < 1 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: N=%d (need 1 <= N <= 2^30)", N);
+    if (k < 1 || k > N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: k=%d out of range for %d values (need 1 <= k <= N)", k, N);
+    if (!values || !workspace || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: values, workspace or out is NULL");
+    GSR_HIP(gsi_kth_launch(N, k, values, workspace, out, (hipStream_t)stream), "kth smallest");
+    return GSR_OK;
+}
+
+extern "C" int gsr_scene_init_fill(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
+                                   float* anchor_feat, float* rotation, float* opacity_out, float* uncertainty_out, float* max_radii2D,
+                                   float* xyz_max, void* stream)
+{
+    if (M < 0 || K < 0 || F < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: M=%d K=%d F=%d (need all >= 0)", M, K, F);
+    const int64_t widest = (int64_t)M * (3 * (int64_t)K > (int64_t)F ? (3 * (int64_t)K > 6 ? 3 * (int64_t)K : 6) : ((int64_t)F > 6 ? (int64_t)F : 6));
+    if (widest >= 0x7fffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: M=%d K=%d F=%d (need M * max(3 K, F, 6) < 2^31)", M, K, F);
+    if (!xyz_max) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: xyz_max is NULL");
+    if (M > 0 && (!anchors || !dist2 || !scaling || !rotation || !opacity_out || !uncertainty_out || !max_radii2D || (K > 0 && !offset)
+                  || (F > 0 && !anchor_feat)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: a required pointer is NULL");
+    GSR_HIP(gsi_fill_launch(M, K, F, anchors, dist2, opacity, scaling, offset, anchor_feat, rotation, opacity_out, uncertainty_out, max_radii2D,
+                            xyz_max, (hipStream_t)stream),
+            "scene init fill");
+    return GSR_OK;
+}
+
 // ---- neural-Gaussian decode (decode.hip) ----
 static int gsr_check_decode(int N, int K, const float* const* weights)
 {

@@ -468,6 +468,17 @@ hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* ancho
 hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows, const uint8_t* offset_mask,
                              int L0, const uint8_t* reset, hipStream_t stream);
 
+// ---- scene_init.hip (voxelize_sample / create_from_pcd: 64-bit key sort, voxel dedupe, k-th smallest, initial state; validated by the caller) ----
+size_t gsi_sort_workspace_bytes(int N);
+hipError_t gsi_sort_launch(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, hipStream_t stream);
+size_t gsi_voxelize_workspace_bytes(int N);
+hipError_t gsi_voxelize_launch(int N, int fp64, const void* points, double v_host, const float* v_dev, void* workspace, void* out,
+                               int32_t* info, hipStream_t stream);
+size_t gsi_kth_workspace_bytes(int N);
+hipError_t gsi_kth_launch(int N, int k, const float* values, void* workspace, float* out, hipStream_t stream);
+hipError_t gsi_fill_launch(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
+                           float* feat, float* rotation, float* opac, float* unc, float* radii, float* xyz_max, hipStream_t stream);
+
 // adam.hip: one launch for all tensors (validated by the caller; tensors with n == 0 are skipped)
 hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_t stream);
 

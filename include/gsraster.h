@@ -644,6 +644,56 @@ size_t gsr_knn_workspace_bytes(int P);
 int gsr_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream);
 
 /*
+ * ---- scene initialisation (scene_init.hip): point cloud -> anchors -> the state create_from_pcd leaves ------------------------
+ * Replaces GaussianModel.voxelize_sample and create_from_pcd (scene/gaussian_model.py:295-345).  All four calls launch on `stream`,
+ * never allocate or synchronise and read nothing back; every counter and scan is an integer one, so the same inputs give the same
+ * bits.  Workspaces: the *_workspace_bytes query of the call (0 for sizes the call rejects), written before they are read.
+ *
+ * gsr_sort_keys_u64: keys_out = the N unsigned 64-bit keys of keys_in in ascending order (all 64 bits significant; stable, which
+ * a key-only sort cannot show but its users may rely on once it carries a payload).  keys_in == keys_out sorts in place.  LSD radix,
+ * eight 8-bit digits; a workgroup ranks GSR_SORT_BLOCK_KEYS keys.  A pass whose digit is the same in every key is skipped; that is
+ * decided on the device.  0 <= N <= 2^30.
+ *
+ * gsr_voxelize: points [N,3], fp32 (fp64 = 0) or fp64 (fp64 = 1); out [N,3] of the same type, of which the first M rows are written.
+ * The voxel size v is the host double `voxel_size`, or, when voxel_size_dev is not NULL, the fp32 word it points to on the device.
+ *     cell   r = round_half_even(p / v) per component, in the input's precision: fp32 input divides by (float) v (one IEEE fp32
+ *            division, rintf), fp64 input by v in fp64 (rint).  -0.0 and +0.0 are the cell 0.
+ *     key    (x - xmin, y - ymin, z - zmin) packed x-major into 64 bits; a field is as wide as its axis' range of cells needs
+ *            (0 bits for a constant axis); minima and maxima are found on the device.
+ *     rows   one per distinct key, in ascending key order = lexicographic (x, y, z) = the row order of numpy.unique(axis=0);
+ *            value (T) cell * (T) v, one rounded product.
+ * info (device int32 [4]) = {M, flags, the bits of (float) v, 0}.  A flag means the rows are not valid:
+ *     GSR_VOXELIZE_NONFINITE   a quotient was NaN or infinite (a non-finite point, or v = 0 or NaN)
+ *     GSR_VOXELIZE_CELL_RANGE  a cell index of magnitude >= 2^31
+ *     GSR_VOXELIZE_KEY_WIDTH   the three field widths sum to more than 64 bits
+ * 0 <= N <= 2^30.
+ *
+ * gsr_kth_smallest_f32: *out (device) = the k-th smallest (1-based, 1 <= k <= N) of N fp32 values = torch.kthvalue(v, k).values
+ * (every NaN ordered last).  A radix select over four 8-bit digits of an order-preserving image of the bit patterns.
+ *
+ * gsr_scene_init_fill: one launch.  anchors [M,3], dist2 [M] (gsr_knn_mean_dist2 of the anchors) ->
+ *     scaling [M,6] = logf(sqrtf(max(dist2, 1e-7f))) in all six columns;  offset [M,K,3] = 0;  anchor_feat [M,F] = 0;
+ *     rotation [M,4] = (1, 0, 0, 0);  opacity, uncertainty [M,1] = `opacity` (the caller's inverse_sigmoid(0.1));
+ *     max_radii2D [M] = 0;  xyz_max [3] = the column maxima of anchors (-inf for M = 0; -0.0 counts as +0.0).
+ * M * max(3 K, F, 6) < 2^31.
+ */
+#define GSR_SORT_BLOCK_KEYS 2048
+#define GSR_VOXELIZE_NONFINITE  1
+#define GSR_VOXELIZE_CELL_RANGE 2
+#define GSR_VOXELIZE_KEY_WIDTH  4
+int gsr_sort_block_keys(void); /* GSR_SORT_BLOCK_KEYS of the library */
+size_t gsr_sort_keys_workspace_bytes(int N);
+int gsr_sort_keys_u64(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, void* stream /* hipStream_t */);
+size_t gsr_voxelize_workspace_bytes(int N);
+int gsr_voxelize(int N, int fp64, const void* points, double voxel_size, const float* voxel_size_dev /* or NULL */, void* workspace,
+                 void* out /* [N,3] */, int32_t* info /* [4] */, void* stream);
+size_t gsr_kth_smallest_workspace_bytes(int N);
+int gsr_kth_smallest_f32(int N, int k, const float* values, void* workspace, float* out, void* stream);
+int gsr_scene_init_fill(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
+                        float* anchor_feat, float* rotation, float* opacity_out, float* uncertainty_out, float* max_radii2D,
+                        float* xyz_max, void* stream);
+
+/*
  * Optional per-stage timing (bench.py's roofline numbers; the reference has no counterpart -- its only
  * timing is two CUDA events around a whole training iteration, train.py:343-344,406,578).
  * Between gsr_profile_begin() and gsr_profile_end() every stage of every call is bracketed by a pair
