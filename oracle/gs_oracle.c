@@ -6,12 +6,14 @@
  * and bench.py's cpu_baseline leg may load it.  The product path (gscream_amd/) never
  * links, imports or calls anything in oracle/.
  *
- * PARITY STATUS: *parity unpinned*.  The reference ships no tests, golden vectors or
- * fixtures for this path and its implementation is CUDA-only
- * (needs nvcc + the CUDA runtime headers + CUB, none of which exist in this image), so it
- * cannot be built or run here without writing stand-ins for those headers -- which the
- * task forbids.  The only reference-derived numbers available are the five filter-API
- * known answers recorded in SURVEY.md Appendix B-6; tests/test_oracle.py checks them.
+ * PARITY STATUS: held against the reference's own kernels on the GPU.  The reference ships
+ * no tests, golden vectors or fixtures for this path, but its
+ * three .cu files compile unedited for gfx950 behind stand-in CUDA headers (oracle/ref_cuda,
+ * `make ref`); tests/test_gpu_reference_kernels.py requires this file's per-Gaussian stage
+ * and binning to equal theirs bit for bit and puts their blend and backward through the
+ * strict parity gate.  Not pinned by that: CUDA's own libm and nvcc's FMA contraction.
+ * On the CPU the reference-derived numbers are the five filter-API known answers recorded
+ * in SURVEY.md Appendix B-6; tests/test_oracle.py checks them.
  * Two pieces of the path ARE pinned by vectors the reference's own importable Python
  * computed in the build container (tests/golden/make_reference_vectors.py ->
  * tests/golden/ref_camera.npz, ref_sh.npz; checked by tests/test_reference_vectors.py):

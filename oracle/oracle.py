@@ -2,9 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY -- see the header of gs_oracle.c.  Only tests/, the smoke check in
 __graft_entry__.py and bench.py's cpu_baseline leg import this module.  Parity status of the
-oracle itself: *parity unpinned* (the reference ships no golden vectors and cannot be built
-here), except the camera convention and the SH colours, which tests/test_reference_vectors.py
-pins with vectors the reference's own Python helpers computed; see DESIGN.md section "Oracle".
+oracle itself: held against the reference's own kernels, compiled for gfx950 (oracle/ref_cuda.py,
+tests/test_gpu_reference_kernels.py); on the CPU the camera convention and the SH colours are
+pinned by tests/test_reference_vectors.py with vectors the reference's own Python helpers
+computed; see DESIGN.md section "Oracle".
 
 The call structure mirrors the reference's C++ entry points
 (DGR/rasterize_points.cu:35-122 forward, :124-211 backward, :213-373 filters), with numpy
@@ -211,7 +212,8 @@ def backward_envelope(st, gids, means3D, scales, rotations, dL_dcolor, dL_ddepth
                dL_dopacity=np.zeros((ng, K, 1), np.float32), dL_duncertainty=np.zeros((ng, K, 1), np.float32),
                dL_dmeans3D=np.zeros((ng, K, 3), np.float32), dL_dcov3D=np.zeros((ng, K, 6), np.float32),
                dL_dscales=np.zeros((ng, K, 3), np.float32), dL_drotations=np.zeros((ng, K, 4), np.float32),
-               dL_dsh=np.zeros((ng, K, M, 3), np.float32))
+               dL_dsh=np.zeros((ng, K, M, 3), np.float32),
+               dL_dconic=np.zeros((ng, K, 3), np.float32), dL_ddepths=np.zeros((ng, K, 1), np.float32))  # (the two internal sums)
     if ng == 0:
         return fam
     most = L.gso_backward_envelope(
@@ -240,6 +242,8 @@ def backward_envelope(st, gids, means3D, scales, rotations, dL_dcolor, dL_ddepth
         fam["dL_dcolors"][:, k] = sums[:ng, k, 6:9]
         fam["dL_dopacity"][:, k, 0] = sums[:ng, k, 5]
         fam["dL_duncertainty"][:, k, 0] = sums[:ng, k, 10]
+        fam["dL_dconic"][:, k] = sums[:ng, k, 2:5]
+        fam["dL_ddepths"][:, k, 0] = sums[:ng, k, 9]
         fam["dL_dmeans3D"][:, k] = o["m3"]; fam["dL_dcov3D"][:, k] = o["cov"]; fam["dL_dscales"][:, k] = o["sc"]
         fam["dL_drotations"][:, k] = o["ro"]; fam["dL_dsh"][:, k] = o["sh"]
     return fam

@@ -4,7 +4,8 @@ Run in the build container:  python tests/golden/make_golden.py
 The oracle (oracle/gs_oracle.c) is a restatement of the reference, not the reference itself, and
 the reference ships no golden vectors, so these fixtures pin the ORACLE (regression
 pin for tests/test_oracle.py) and give the GPU tests vectors that need no oracle at run time.
-They do not upgrade the oracle's status from "parity unpinned".  Cases follow SURVEY 8(c)'s list.
+They are the oracle's output, not the reference's: what holds the oracle to the reference's own kernels on these same
+inputs is tests/test_gpu_reference_kernels.py.  Cases follow SURVEY 8(c)'s list.
 """
 import os
 import sys

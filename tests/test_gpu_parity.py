@@ -5,7 +5,6 @@ Bars (BASELINE.json north_star): integer results (radii, num_rendered, per-tile 
 images within 1e-4 abs; gradients within 1e-3 rel (denominator |ref| + 1e-3 max|ref|)."""
 import os
 import sys
-import zlib
 
 import numpy as np
 import pytest
@@ -578,40 +577,9 @@ def _vs_oracle(s, grads, name, img_frac=2e-5):
     return st, got
 
 
-@pytest.mark.parametrize("variant", ["scale_modifier", "sh_deg0", "sh_deg1", "sh_deg2", "huge_gaussians", "opacity_edges",
-                                     "thin_image", "tall_image", "tiny_gaussians"])
+@pytest.mark.parametrize("variant", Hh.VARIANTS)
 def test_more_cases_against_live_oracle(variant):
-    rng = np.random.default_rng(zlib.crc32(variant.encode()) % 1000)  # (str hash() is salted per process: not a seed)
-    if variant == "scale_modifier":
-        s = S.scene_config1(seed=80, P=1500, W=120, H=90)
-        s["scale_modifier"] = 0.6
-    elif variant.startswith("sh_deg"):
-        deg = int(variant[-1])
-        s = S.scene_config1(seed=81 + deg, P=1200, W=112, H=80, w2c=S.random_w2c(rng))
-        s["shs"] = rng.normal(0, 0.35, size=(1200, (deg + 1) ** 2, 3)).astype(np.float32)
-        s["sh_degree"] = deg
-        del s["colors"]
-    elif variant == "huge_gaussians":
-        # rectangles far beyond 64 tiles (the tile-cull mask covers the first 64; the rest is always binned)
-        s = S.scene_config1(seed=85, P=300, W=320, H=256)
-        s["scales"][:40] = rng.uniform(0.8, 2.5, size=(40, 3)).astype(np.float32)
-        s["opacities"][:40] = rng.uniform(0.02, 0.6, size=(40, 1)).astype(np.float32)
-    elif variant == "opacity_edges":
-        s = S.scene_config1(seed=86, P=1500, W=120, H=90)
-        s["opacities"][:300:6] = 0.0
-        s["opacities"][1:300:6] = 1.0 / 255.0
-        s["opacities"][2:300:6] = 0.0039
-        s["opacities"][3:300:6] = 1.0
-        s["opacities"][4:300:6] = 3.0     # alpha clamps at 0.99
-        s["opacities"][5:300:6] = -0.5    # never blended
-    elif variant == "thin_image":
-        s = S.scene_config1(seed=87, P=800, W=200, H=3)
-    elif variant == "tall_image":
-        s = S.scene_config1(seed=88, P=800, W=5, H=130)
-    else:
-        s = S.scene_config1(seed=89, P=3000, W=150, H=100)
-        s["scales"] *= 0.01   # sub-pixel: the 0.3 low-pass dominates
-    grads = S.upstream_grads(90, s["W"], s["H"])
+    s, grads = Hh.variant_scene(variant)
     st, got = _vs_oracle(s, grads, variant)
     if variant == "huge_gaussians":
         gx, gy = (s["W"] + 15) // 16, (s["H"] + 15) // 16
