@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "gsr_depth_points", "gsr_point_normals",
     "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
     "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
+    "gsr_png_capacity", "gsr_png_workspace_bytes", "gsr_png_encode",
     "gsr_sort_block_keys", "gsr_sort_keys_workspace_bytes", "gsr_sort_keys_u64", "gsr_voxelize_workspace_bytes", "gsr_voxelize",
     "gsr_kth_smallest_workspace_bytes", "gsr_kth_smallest_f32", "gsr_scene_init_fill",
 )
@@ -76,6 +77,7 @@ class FramePanel(ctypes.Structure):
 
 
 FRAME_MAX_PANELS = 8
+PNG_CHUNK, PNG_HEADER_BYTES, PNG_FILTER_ADAPTIVE = 32768, 16, 5  # GSR_PNG_* of include/gsraster.h
 FRAME_QUANT, FRAME_QUANT_CLAMP, FRAME_ABSDIFF, FRAME_NORMAL, FRAME_CMAP_CV, FRAME_CMAP_MPL_ALIGNED, FRAME_CMAP_MPL = range(7)
 
 
@@ -220,6 +222,12 @@ def load():
     lib.gsr_frame_stats.argtypes = [_c_int] * 3 + [_vp] * 7
     lib.gsr_frame_compose.restype = _c_int
     lib.gsr_frame_compose.argtypes = [_c_int] * 5 + [ctypes.POINTER(FramePanel)] + [_vp] * 3
+    lib.gsr_png_capacity.restype = ctypes.c_size_t
+    lib.gsr_png_capacity.argtypes = [_c_int] * 3
+    lib.gsr_png_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_png_workspace_bytes.argtypes = [_c_int] * 4
+    lib.gsr_png_encode.restype = _c_int
+    lib.gsr_png_encode.argtypes = [_vp, ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 5 + [_vp, ctypes.c_size_t, _vp, _vp]
     lib.gsr_sort_block_keys.restype = _c_int
     lib.gsr_sort_block_keys.argtypes = []
     for name in ("gsr_sort_keys_workspace_bytes", "gsr_voxelize_workspace_bytes", "gsr_kth_smallest_workspace_bytes"):

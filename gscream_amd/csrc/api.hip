@@ -1234,3 +1234,40 @@ extern "C" int gsr_frame_compose(int B, int H, int W_out, int channels_out, int 
     GSR_HIP(frames_launch_compose(B, H, W_out, channels_out, n, panels, params, out, dwords, (hipStream_t)stream), "frame compose");
     return GSR_OK;
 }
+
+// ---- PNG encoding (png.hip) ----
+static int png_check_sizes(int B, int H, int W, int C)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: B=%d H=%d W=%d (need all > 0)", B, H, W);
+    if (C != 1 && C != 3 && C != 4) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: C=%d (need 1, 3 or 4)", C);
+    if (B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: B=%d has too many pictures (need B <= 65535)", B);
+    if ((int64_t)W * C >= (1 << 24)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: W=%d C=%d has too long a row (need W*C < 2^24)", W, C);
+    if ((int64_t)H * ((int64_t)W * C + 1) >= 0x70000000LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: H=%d W=%d C=%d has too many bytes (need H*(1 + W*C) < 0x70000000)", H, W, C);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_png_capacity(int H, int W, int C) { return png_check_sizes(1, H, W, C) ? 0 : png_layout(H, W, C).capacity; }
+
+extern "C" size_t gsr_png_workspace_bytes(int B, int H, int W, int C)
+{
+    return png_check_sizes(B, H, W, C) ? 0 : (size_t)B * png_layout(H, W, C).per_picture;
+}
+
+extern "C" int gsr_png_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
+                              uint8_t* out, size_t out_stride, void* workspace, void* stream)
+{
+    if (int rc = png_check_sizes(B, H, W, C)) return rc;
+    if (!images || !out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: images, out or workspace is NULL");
+    if (filter < 0 || filter > GSR_PNG_FILTER_ADAPTIVE)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: filter=%d (need 0 .. 4 or GSR_PNG_FILTER_ADAPTIVE)", filter);
+    if (row_stride < (long long)W * C) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: row_stride=%lld is below W*C=%lld", row_stride, (long long)W * C);
+    if (B > 1 && image_stride < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: image_stride=%lld is negative", image_stride);
+    const size_t need = GSR_PNG_HEADER_BYTES + png_layout(H, W, C).capacity;
+    if (out_stride < need || out_stride % 4 || ((uintptr_t)out & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: out_stride=%zu (need >= %zu = header + capacity, a multiple of 4) or out is not 4-byte aligned",
+                        out_stride, need);
+    if ((uintptr_t)workspace & 15) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: workspace is not 16-byte aligned");
+    GSR_HIP(png_launch_encode(images, row_stride, image_stride, B, H, W, C, filter, out, out_stride, workspace, (hipStream_t)stream), "png encode");
+    return GSR_OK;
+}

@@ -502,3 +502,15 @@ hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const fl
                                double* stats, float* params, hipStream_t stream);
 hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
                                  uint8_t* out, bool dwords, hipStream_t stream);
+
+// png.hip: uint8 pictures -> PNG files (validated by the caller).  The workspace holds, per picture, the filtered stream, the rows' Adler-32
+// partials (two words each), the chunks' byte counts and one slot of PNG_SLOT_BYTES per chunk (the chunk's deflate bytes).
+#define PNG_SLOT_BYTES (GSR_PNG_CHUNK + 32)
+struct PngLayout {
+    size_t row_bytes, stream_bytes, chunks;             // 1 + W*C, H * row_bytes, ceil(stream_bytes / GSR_PNG_CHUNK)
+    size_t adler_off, sizes_off, slots_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
+    size_t capacity;                                    // what a file can take at most (every chunk stored)
+};
+PngLayout png_layout(int H, int W, int C);
+hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
+                             uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream);

@@ -1,5 +1,6 @@
 """render_set's output frames on the HIP path: what train.py:710-848 does between the render and the PNG, as finished uint8 pictures
-on the device, in HWC order, ready for one D2H copy and a PNG encoder.
+on the device, in HWC order, ready for one D2H copy and a PNG encoder -- or for gscream_amd.png (INTEGRATION U), which encodes them
+where they are.
 
 Integration is a handful of rebindings in render_set (INTEGRATION S):
 

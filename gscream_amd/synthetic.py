@@ -227,3 +227,37 @@ def upstream_grads(seed, W, H, color=True, depth=True, unc=True):
     gd = rng.normal(size=(1, H, W)).astype(np.float32) / n if depth else np.zeros((1, H, W), np.float32)
     gu = rng.normal(size=(1, H, W)).astype(np.float32) / n if unc else np.zeros((1, H, W), np.float32)
     return gc, gd, gu
+
+
+def picture(kind, H, W, C=3, seed=0):
+    """Finished uint8 pictures [H, W, C] (C = 1, 3, 4) with the content render_set writes, for the PNG encoder's tests and
+    tools/png_bench.py: "texture" -- a render: smooth shading, fine procedural detail and sensor-like noise; "colormap" -- a smooth
+    field through a colour ramp, as the depth pictures; "mask" -- a binary object mask; "constant" -- one value (a saturated panel);
+    "noise" -- uniform random bytes.  With C = 4 the last channel is 255."""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    colours = min(C, 3)
+    if kind == "texture":
+        planes = []
+        for c in range(colours):
+            shade = 0.5 + 0.25 * np.sin(0.011 * j + 0.7 * c) * np.cos(0.013 * i - 0.4 * c) + 0.1 * np.sin(0.37 * i + 0.29 * j + c)
+            detail = 0.06 * np.sin(1.9 * i + 0.3 * c) * np.sin(2.3 * j) + 0.03 * rng.standard_normal((H, W))
+            planes.append(shade + detail)
+        img = np.stack(planes, -1)
+    elif kind == "colormap":
+        field = 0.5 + 0.3 * np.sin(0.004 * j + 0.3) * np.cos(0.006 * i) + 0.2 * (j / max(W - 1, 1)) - 0.1 * (i / max(H - 1, 1))
+        ramp = np.stack([field, np.sin(np.pi * field), 1.0 - field], -1)
+        img = ramp[..., :colours] if colours > 1 else field[..., None]
+    elif kind == "mask":
+        blob = ((i - 0.45 * H) / (0.3 * H + 1)) ** 2 + ((j - 0.55 * W) / (0.25 * W + 1)) ** 2 + 0.15 * np.sin(0.05 * i) * np.sin(0.04 * j)
+        img = np.repeat((blob < 1.0).astype(np.float64)[..., None], colours, -1)
+    elif kind == "constant":
+        img = np.full((H, W, colours), 0.5)
+    elif kind == "noise":
+        return rng.integers(0, 256, (H, W, C), dtype=np.uint8)
+    else:
+        raise ValueError(f"picture: kind {kind!r}")
+    out = np.clip(img * 255.0 + 0.5, 0, 255).astype(np.uint8)
+    if C == 4:
+        out = np.concatenate([out, np.full((H, W, 1), 255, np.uint8)], -1)
+    return np.ascontiguousarray(out)

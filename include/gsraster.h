@@ -597,6 +597,64 @@ int gsr_frame_compose(int B, int H, int W_out, int channels_out, int n, const gs
                       const float* params /* [B,8] or NULL */, uint8_t* out /* [B,H,W_out,channels_out] */, void* stream /* hipStream_t */);
 
 /*
+ * ---- PNG encoding (png.hip): the finished uint8 pictures -> the bytes of their .png files, on the device ----------------------
+ * Replaces the encoder behind torchvision.utils.save_image, cv2.imwrite and plt.imsave in render_set (train.py:776-834).  A file
+ * made here is a plain PNG that any decoder reads to the exact pixels; which of the many valid files it is, is fixed by these rules:
+ *
+ *   container  the 8 signature bytes, IHDR, one IDAT per deflate chunk, IEND; no ancillary chunks.  IHDR: width, height, bit depth 8,
+ *              colour type 0 / 2 / 6 for C = 1 / 3 / 4, compression 0, filter method 0, no interlace.  Every chunk carries the CRC-32
+ *              of its type and data.  The Adler-32 closes the last IDAT.
+ *   zlib       the bytes 78 01, the deflate data, the Adler-32 of the filtered stream S, big-endian.
+ *   S          H (1 + W C) bytes: per row the filter type, then the W C residuals with bpp = C; the row above the first is zeros.
+ *              residual = (x - predictor) mod 256; the predictor of type 0 is 0, of 1 the byte a to the left (bpp back; 0 in the first
+ *              pixel), of 2 the byte b above, of 3 floor((a + b) / 2), of 4 Paeth's: with c the byte above a and p = a + b - c, a
+ *              when |p - a| <= |p - b| and |p - a| <= |p - c|, else b when |p - b| <= |p - c|, else c.
+ *   filter     0 .. 4: that type in every row.  GSR_PNG_FILTER_ADAPTIVE: per row the type with the smallest sum over the row of
+ *              |signed residual| (r < 128 ? r : 256 - r), ties to the lowest type (libpng's heuristic, stated as a rule).
+ *   chunks     S is cut every GSR_PNG_CHUNK bytes, wherever that falls in a row.  A chunk is a deflate sequence of its own: nothing
+ *              refers across a cut, and every chunk starts on a byte boundary.
+ *   tokens     the first byte of a chunk is a literal.  A maximal run of L equal bytes is its first byte as a literal, then its
+ *              L - 1 repeats cut into pieces of 258 from the front: a piece of 3 .. 258 is one match of that length at distance 1,
+ *              a piece of 1 or 2 is literals.  (The greedy rule of zlib's Z_RLE strategy.)  Then the end-of-block symbol.
+ *   block      one dynamic-Huffman block (BTYPE 10) or one stored block (BTYPE 00) per chunk, whichever has fewer bits, counted
+ *              exactly; a tie is stored.  No fixed blocks.  A chunk that is not the last is followed by an empty stored block
+ *              (BFINAL 0, BTYPE 00, padding to the byte, 00 00 FF FF); the last chunk's block has BFINAL set and is padded with zeros.
+ *   codes      literal / length: Huffman's code lengths by a two-queue merge of the used symbols in ascending (count, symbol) order,
+ *              a leaf before an internal node of the same weight; lengths beyond 15 are folded to 15, then, while the Kraft sum
+ *              exceeds 1, one code of length 15 is taken away and one code of the greatest length below 15 that occurs becomes two
+ *              codes one bit longer; the lengths go to the symbols longest first in ascending (count, symbol) order.  Kraft sum = 1
+ *              exactly.  Canonical codes as RFC 1951 3.2.2.  Distance: HDIST = 1 code; its length is 1 when the chunk has a match
+ *              (RFC 1951 3.2.7's single code of one bit, sent as 0), else 0.  Code-length code: the same construction with the limit
+ *              7; if only one of its symbols occurs, symbol 0 (or 1, if that one is 0) also gets length 1 so that the code is
+ *              complete.  HLIT = 257 or the last used length symbol + 1; HCLEN drops the trailing zeros of the permuted order.
+ *   header     the HLIT + 1 code lengths as one sequence (runs cross into the distance code): a run of r zeros is, while r >= 3,
+ *              symbol 17 (3 .. 10) or 18 (11 .. 138) for min(r, 138), then single zeros; a run of r equal nonzero lengths is the
+ *              length once, then symbol 16 for min(r', 6) while the rest r' >= 3, then the length itself.
+ *
+ * gsr_png_capacity(H, W, C): what a file can take when every chunk is stored,
+ *     8 + 25 + chunks (12 + 5 + 5) + H (1 + W C) + 2 + 4 + 12,   chunks = ceil(H (1 + W C) / GSR_PNG_CHUNK);
+ * no file is larger.  0 for sizes the call rejects, as gsr_png_workspace_bytes.
+ *
+ * gsr_png_encode: images are B pictures of uint8 [H, W, C], pixel (b, y, x, c) at images[b*image_stride + y*row_stride + x*C + c]
+ * (strides in bytes): the inner two dimensions are dense, the row stride is free (>= W C), so a panel of a wider sheet is read in
+ * place.  Picture b's result is out + b*out_stride: GSR_PNG_HEADER_BYTES of header -- four uint32 words {the file's byte count, its
+ * number of IDAT chunks, 0, 0} -- then the file.  Nothing behind the file's last byte is written.  out_stride >= header +
+ * capacity and a multiple of 4, out 4-byte aligned, workspace 16-byte aligned and of gsr_png_workspace_bytes(B, H, W, C) bytes,
+ * written before it is read.  Three launches on `stream` (filter: a workgroup per row; deflate: a workgroup per chunk with the
+ * chunk and its output in LDS; assemble: a workgroup per IDAT, CRC-32 by slices combined through x^(8n) mod P); no synchronisation,
+ * nothing read back, no dependency between workgroups, the same bytes for the same input.
+ * Rejected before launching (GSR_ERR_INVALID_ARGUMENT): NULL pointers; B, H or W <= 0; C other than 1, 3, 4; B > 65535; W C >= 2^24;
+ * H (1 + W C) >= 0x70000000; a filter outside 0 .. 5; row_stride < W C; a negative image_stride; out_stride or an alignment as above.
+ */
+#define GSR_PNG_CHUNK 32768
+#define GSR_PNG_HEADER_BYTES 16
+#define GSR_PNG_FILTER_ADAPTIVE 5
+size_t gsr_png_capacity(int H, int W, int C);
+size_t gsr_png_workspace_bytes(int B, int H, int W, int C);
+int gsr_png_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
+                   uint8_t* out, size_t out_stride, void* workspace, void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
