@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
     "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
     "gsr_png_capacity", "gsr_png_workspace_bytes", "gsr_png_encode",
+    "gsr_png_decode_workspace_bytes", "gsr_png_decode",
     "gsr_sort_block_keys", "gsr_sort_keys_workspace_bytes", "gsr_sort_keys_u64", "gsr_voxelize_workspace_bytes", "gsr_voxelize",
     "gsr_kth_smallest_workspace_bytes", "gsr_kth_smallest_f32", "gsr_scene_init_fill",
 )
@@ -78,6 +79,10 @@ class FramePanel(ctypes.Structure):
 
 FRAME_MAX_PANELS = 8
 PNG_CHUNK, PNG_HEADER_BYTES, PNG_FILTER_ADAPTIVE = 32768, 16, 5  # GSR_PNG_* of include/gsraster.h
+PNG_PIECE_IDAT, PNG_PIECE_START = 1, 2
+PNG_STATUS = ("ok", "truncated", "reserved block type", "stored LEN/NLEN mismatch", "over-subscribed or incomplete code", "invalid symbol",
+              "distance before the start of the stream", "stream longer than the picture's", "stream shorter than the picture's",
+              "filter byte above 4", "Adler-32 mismatch", "CRC-32 mismatch", "table entry out of bounds")  # GSR_PNG_OK .. GSR_PNG_TABLE
 FRAME_QUANT, FRAME_QUANT_CLAMP, FRAME_ABSDIFF, FRAME_NORMAL, FRAME_CMAP_CV, FRAME_CMAP_MPL_ALIGNED, FRAME_CMAP_MPL = range(7)
 
 
@@ -228,6 +233,10 @@ def load():
     lib.gsr_png_workspace_bytes.argtypes = [_c_int] * 4
     lib.gsr_png_encode.restype = _c_int
     lib.gsr_png_encode.argtypes = [_vp, ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 5 + [_vp, ctypes.c_size_t, _vp, _vp]
+    lib.gsr_png_decode_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_png_decode_workspace_bytes.argtypes = [ctypes.c_size_t, _c_int, _c_int]
+    lib.gsr_png_decode.restype = _c_int
+    lib.gsr_png_decode.argtypes = [_vp, ctypes.c_size_t, _vp, _c_int, _vp, _c_int, _c_int, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, _vp]
     lib.gsr_sort_block_keys.restype = _c_int
     lib.gsr_sort_block_keys.argtypes = []
     for name in ("gsr_sort_keys_workspace_bytes", "gsr_voxelize_workspace_bytes", "gsr_kth_smallest_workspace_bytes"):

@@ -1271,3 +1271,29 @@ extern "C" int gsr_png_encode(const uint8_t* images, long long row_stride, long 
     GSR_HIP(png_launch_encode(images, row_stride, image_stride, B, H, W, C, filter, out, out_stride, workspace, (hipStream_t)stream), "png encode");
     return GSR_OK;
 }
+
+// ---- PNG decoding (png_decode.hip) ----
+extern "C" size_t gsr_png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces)
+{
+    if (nfiles <= 0 || npieces <= 0 || stream_bytes >= ((size_t)1 << 40)) return 0;
+    return png_decode_workspace_bytes(stream_bytes, nfiles, npieces);
+}
+
+extern "C" int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
+                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!bytes || !files || !pieces || !out || !status || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: bytes, files, pieces, out, status or workspace is NULL");
+    if (nfiles <= 0 || npieces <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: nfiles=%d npieces=%d (need both > 0)", nfiles, npieces);
+    if (nbytes >= ((size_t)1 << 32) || out_bytes >= ((size_t)1 << 32))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: nbytes=%zu out_bytes=%zu (need both < 2^32)", nbytes, out_bytes);
+    if (((uintptr_t)bytes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)files & 7) || ((uintptr_t)pieces & 7) ||
+        ((uintptr_t)status & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: bytes, out and workspace are 16-byte aligned, the tables 8, status 4");
+    if (workspace_bytes < (size_t)npieces * 12 + (size_t)nfiles * 4)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
+    GSR_HIP(png_launch_decode(bytes, nbytes, files, nfiles, pieces, npieces, verify_crc, out, out_bytes, status, workspace, workspace_bytes,
+                              (hipStream_t)stream),
+            "png decode");
+    return GSR_OK;
+}

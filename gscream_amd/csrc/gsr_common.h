@@ -514,3 +514,11 @@ struct PngLayout {
 PngLayout png_layout(int H, int W, int C);
 hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
                              uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream);
+
+// png_decode.hip: PNG files -> uint8 pictures (pointers and counts validated by the caller; the tables are checked on the device).
+// The workspace holds the files' inflated streams, then per piece {size, flag, offset} of the segment that starts there, then per
+// file the Adler-32 of its trailer.
+size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces);
+hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
+                             int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream);

@@ -24,6 +24,7 @@
 
 #include "gsr_common.h"
 #include "gsr_scan.h"
+#include "png_crc.h"
 
 #define PNG_CHUNK GSR_PNG_CHUNK
 #define PNG_FLT_THREADS 256
@@ -32,7 +33,6 @@
 #define PNG_PER (PNG_CHUNK / PNG_DEF_THREADS)  // bytes of a chunk a deflate thread owns
 #define PNG_ADLER 65521u
 #define PNG_LITLEN 286
-#define PNG_POLY 0xEDB88320u
 static_assert(PNG_PER == 32, "a thread's run heads are one 32-bit mask, and at most one 258-byte match starts in its span");
 static_assert(PNG_SLOT_BYTES >= PNG_CHUNK + 2 + 5 + 5 + 4 && PNG_SLOT_BYTES % 16 == 0, "zlib header, stored header, marker, one dword of slack");
 
@@ -505,29 +505,7 @@ __global__ void __launch_bounds__(PNG_DEF_THREADS) png_deflate_kernel(uint8_t* _
     if (tid == 0) ((uint32_t*)(base + lay.sizes_off))[k] = nbytes;
 }
 
-// ---- assemble ----
-// a * b mod P, both in the reflected representation of CRC-32 (bit 31 = x^0)
-__device__ __forceinline__ uint32_t png_gf2_mul(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-#pragma unroll 4
-    for (int i = 0; i < 32; i++) {
-        p ^= (a & (0x80000000u >> i)) ? b : 0u;
-        b = (b & 1u) ? (b >> 1) ^ PNG_POLY : b >> 1;
-    }
-    return p;
-}
-// x^(8 n) mod P
-__device__ __forceinline__ uint32_t png_x8n(uint32_t n)
-{
-    uint32_t r = 0x80000000u, b = 0x00800000u;
-    for (int i = 0; i < 32 && n; i++, n >>= 1) {
-        if (n & 1u) r = png_gf2_mul(r, b);
-        b = png_gf2_mul(b, b);
-    }
-    return r;
-}
-
+// ---- assemble ---- (the CRC's slice arithmetic: png_crc.h)
 __device__ __forceinline__ void png_put_be32(uint8_t* p, uint32_t v)
 {
     p[0] = (uint8_t)(v >> 24);

@@ -655,6 +655,74 @@ int gsr_png_encode(const uint8_t* images, long long row_stride, long long image_
                    uint8_t* out, size_t out_stride, void* workspace, void* stream /* hipStream_t */);
 
 /*
+ * ---- PNG decoding (png_decode.hip, png_inflate.h): the bytes of .png files -> uint8 [H, W, C] pictures, on the device ------------
+ * Replaces Image.open + to_tensor + upload in readImages (train.py:887-902) and Scene's picture loading.  The host reads only the
+ * chunk headers; inflate, Adler-32, unfilter and CRC-32 run on the device, a batch of files of any sizes in one call.
+ *
+ *   accepted   bit depth 8, no interlace, colour type 0 / 2 / 4 / 6 (C = 1 / 3 / 2 / 4); any number of IDAT chunks cut anywhere;
+ *              ancillary chunks (skipped); any conforming zlib stream -- stored, fixed and dynamic blocks, distances to 32768,
+ *              lengths to 258, overlapping copies; the five row filters in any mixture.  Everything else (16-bit and sub-byte depths,
+ *              palette, Adam7, a bad signature or IHDR, no IDAT or IEND, a zlib header that is not deflate with a window of at most
+ *              32 KiB and no dictionary) is the host parser's to reject: the device is never given such a file.
+ *   bytes      the files' bytes, unmodified, back to back in one device buffer of `nbytes`.
+ *   pieces     one gsr_png_piece per chunk of every file, in file order: the offset of the chunk's data in `bytes` (its type is
+ *              the 4 bytes in front, its CRC the 4 bytes behind), the data's length, the file's index, and flags:
+ *              GSR_PNG_PIECE_IDAT; GSR_PNG_PIECE_START on the first IDAT of a file and on every restart candidate.
+ *   segments   an IDAT is a restart candidate when the IDAT before it ends in 00 00 FF FF (an empty stored block: the deflate
+ *              stream is on a byte boundary there).  The candidates cut a file's IDATs into segments.  A file of one segment is
+ *              decoded by one wavefront straight to its stream.  A file of several is measured first: every segment is decoded alone
+ *              for its size only, and flagged when it fails in any way, when a distance reaches before its own first byte, when it
+ *              does not end exactly at its last byte on a block boundary, or when BFINAL comes anywhere but in the last segment.
+ *              No flag: the sizes are scanned and every segment is decoded by a wavefront of its own to its offset (path word 1,
+ *              "parallel").  Any flag: one wavefront decodes the file with all IDATs joined (path word 0, "serial"), in the same
+ *              launch sequence.  The files of gsr_png_encode take the parallel path; a Z_SYNC_FLUSH stream the serial one.
+ *   files      one gsr_png_file per file: H, W, C; its first piece and piece count; its number of segments (START flags); the byte
+ *              offset of its picture in `out` (H W C bytes, dense) and of its inflated stream in the workspace (H (1 + W C) bytes;
+ *              offsets are multiples of 16 and the areas do not overlap).
+ *   status     two int32 per file: {code, path}.  Codes:
+ *                0 GSR_PNG_OK
+ *                1 GSR_PNG_TRUNCATED      the deflate data or the Adler-32 ends early
+ *                2 GSR_PNG_BLOCK_TYPE     block type 3
+ *                3 GSR_PNG_STORED_LEN     a stored block's LEN and NLEN disagree
+ *                4 GSR_PNG_BAD_CODE       an over-subscribed or incomplete code, no end-of-block code, a repeat with nothing before it
+ *                5 GSR_PNG_BAD_SYMBOL     a bit pattern with no symbol, length symbol 286 / 287, distance symbol 30 / 31
+ *                6 GSR_PNG_DISTANCE       a distance before the start of the stream
+ *                7 GSR_PNG_TOO_LONG       the stream is longer than H (1 + W C)
+ *                8 GSR_PNG_TOO_SHORT      ... or shorter
+ *                9 GSR_PNG_FILTER         a filter byte above 4
+ *               10 GSR_PNG_ADLER          the Adler-32 of the inflated stream differs from the trailer
+ *               11 GSR_PNG_CRC            a chunk's CRC-32 differs (verify_crc only; every chunk is checked, also the skipped ones)
+ *               12 GSR_PNG_TABLE          a table entry points outside `bytes`, `out` or the workspace: the file is not touched
+ *              The first failing stage in the order inflate, size, Adler-32, filter, CRC decides.  A failed file's picture is
+ *              unspecified; the other files of the batch are not affected.
+ *   safety     every read is bounded by its piece and by nbytes, every write by the stream's or picture's size, every distance is
+ *              checked against the bytes produced, every loop consumes a bit or produces a byte.  A corrupt file ends in a code.
+ *
+ * gsr_png_decode_workspace_bytes(stream_bytes, nfiles, npieces): stream_bytes = the end of the last stream area.
+ * gsr_png_decode: all pointers are device pointers (bytes, out, workspace 16-byte aligned); launches on `stream` (validate, measure,
+ * plan, inflate, Adler-32, unfilter, CRC-32), allocates nothing, never synchronises, reads nothing back.  Rejected before launching:
+ * NULL pointers, nfiles or npieces <= 0, nbytes or out_bytes of 2^32 or more, a misaligned pointer.
+ */
+#define GSR_PNG_PIECE_IDAT 1u
+#define GSR_PNG_PIECE_START 2u
+typedef struct gsr_png_piece {
+    uint64_t offset;  /* of the chunk's data in `bytes` */
+    uint32_t length, flags, file, reserved;
+} gsr_png_piece;
+typedef struct gsr_png_file {
+    int32_t H, W, C, first_piece, piece_count, segments;
+    uint64_t out_offset, stream_offset;
+} gsr_png_file;
+enum {
+    GSR_PNG_OK = 0, GSR_PNG_TRUNCATED, GSR_PNG_BLOCK_TYPE, GSR_PNG_STORED_LEN, GSR_PNG_BAD_CODE, GSR_PNG_BAD_SYMBOL, GSR_PNG_DISTANCE,
+    GSR_PNG_TOO_LONG, GSR_PNG_TOO_SHORT, GSR_PNG_FILTER, GSR_PNG_ADLER, GSR_PNG_CRC, GSR_PNG_TABLE
+};
+size_t gsr_png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces);
+int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
+                   int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                   void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
