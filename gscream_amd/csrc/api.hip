@@ -560,8 +560,8 @@ extern "C" int gsr_backward(int P, int D, int M, int W, int H, int R, int binnin
                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
                             const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
                             float tan_fovy, const float* dL_dout_color, const float* dL_dout_depth,
-                            const float* dL_dout_feature, const void* geom_ws, const void* image_ws,
-                            const void* binning_ws, void* scratch, float* dL_dmeans2D, float* dL_dcolors,
+                            const float* dL_dout_feature, const void* geom_ws, void* image_ws,
+                            void* binning_ws, void* scratch, float* dL_dmeans2D, float* dL_dcolors,
                             float* dL_dopacity, float* dL_dfeatures, float* dL_dmeans3D, float* dL_dcov3D,
                             float* dL_dsh, float* dL_dscales, float* dL_drotations, const gsr_tuning* tuning, int debug,
                             void* stream_)

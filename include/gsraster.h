@@ -212,7 +212,7 @@ int gsr_backward(int P, int D, int M, int W, int H, int R, int binning_capacity 
                  const float* viewmatrix, const float* projmatrix, const float* campos,
                  float tan_fovx, float tan_fovy,
                  const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_feature,
-                 const void* geom, const void* image, const void* binning, void* scratch,
+                 const void* geom, void* image /* scratch: the task list */, void* binning /* scratch: the slot flags */, void* scratch,
                  float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dfeatures,
                  float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                  const gsr_tuning* tuning, int debug, void* stream);
