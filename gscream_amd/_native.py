@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "gsr_adam_step",
     "gsr_depth_points", "gsr_point_normals",
     "gsr_image_metrics_workspace_bytes", "gsr_image_metrics",
+    "gsr_lpips_workspace_bytes", "gsr_lpips", "gsr_conv3x3_relu",
     "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
     "gsr_png_capacity", "gsr_png_workspace_bytes", "gsr_png_encode",
     "gsr_png_decode_workspace_bytes", "gsr_png_decode",
@@ -221,6 +222,12 @@ def load():
     lib.gsr_image_metrics_workspace_bytes.argtypes = [_c_int] * 4
     lib.gsr_image_metrics.restype = _c_int
     lib.gsr_image_metrics.argtypes = [_c_int] * 4 + [_vp] * 3 + [ctypes.c_longlong] * 2 + [_c_int] + [_vp] * 4
+    lib.gsr_lpips_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_lpips_workspace_bytes.argtypes = [_c_int] * 3
+    lib.gsr_lpips.restype = _c_int
+    lib.gsr_lpips.argtypes = [_c_int] * 3 + [_vp, _vp, _c_int] + [_vp] * 4 + [ctypes.c_longlong] + [_vp] * 6
+    lib.gsr_conv3x3_relu.restype = _c_int
+    lib.gsr_conv3x3_relu.argtypes = [_c_int] * 5 + [_vp] * 4 + [_c_int, _vp]
     lib.gsr_frame_stats_workspace_bytes.restype = ctypes.c_size_t
     lib.gsr_frame_stats_workspace_bytes.argtypes = [_c_int] * 3
     lib.gsr_frame_stats.restype = _c_int

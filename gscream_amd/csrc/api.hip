@@ -1168,6 +1168,53 @@ extern "C" int gsr_image_metrics(int B, int C, int H, int W, const float* pred, 
     return GSR_OK;
 }
 
+// ---- LPIPS (lpips.hip) ----
+static int lpips_check_sizes(int B, int H, int W)
+{
+    if (B <= 0 || B > 32767) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: B=%d (need 1 .. 32767 views: 2B images are one batch)", B);
+    if (H < 16 || W < 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d (need both >= 16: four 2x2 pools)", H, W);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d has too many pixels (need H*W < 2^31 - 256)", H, W);
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_lpips_workspace_bytes(int B, int H, int W)
+{
+    if (lpips_check_sizes(B, H, W)) return 0;
+    return lpips_workspace_bytes(B, H, W);
+}
+
+extern "C" int gsr_lpips(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
+                         const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
+                         float* out_layers, float* out_masked, float* out_spatial, void* stream)
+{
+    if (int rc = lpips_check_sizes(B, H, W)) return rc;
+    if (!in0 || !in1 || !conv_weights || !conv_bias || !lin_weights || !workspace || !out_plain)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: in0, in1, conv_weights, conv_bias, lin_weights, workspace or out_plain is NULL");
+    if (flags & ~GSR_LPIPS_NORMALIZE) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: unknown flag bits in %d", flags);
+    if (mask_stride_b < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: negative mask stride %lld", mask_stride_b);
+    GSR_HIP(lpips_launch(B, H, W, in0, in1, flags, conv_weights, conv_bias, lin_weights, mask, mask_stride_b, workspace, out_plain, out_layers,
+                         out_masked, out_spatial, (hipStream_t)stream),
+            "lpips");
+    return GSR_OK;
+}
+
+extern "C" int gsr_conv3x3_relu(int B, int Cin, int Cout, int H, int W, const float* in, const float* weights_packed, const float* bias,
+                                float* out, int flags, void* stream)
+{
+    if (B <= 0 || B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: B=%d (need 1 .. 65535 images)", B);
+    if (Cin <= 0 || Cout <= 0 || Cout % LPIPS_CONV_NB != 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: Cin=%d Cout=%d (need Cin > 0 and Cout a positive multiple of %d)", Cin, Cout, LPIPS_CONV_NB);
+    if (Cin > 65536 || Cout > 65536) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: Cin=%d Cout=%d is too wide", Cin, Cout);
+    if (H <= 0 || W <= 0 || (int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: H=%d W=%d (need both > 0 and H*W < 2^31 - 256)", H, W);
+    if (!in || !weights_packed || !bias || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: in, weights_packed, bias or out is NULL");
+    if (flags & ~(GSR_LPIPS_NORMALIZE | GSR_LPIPS_SCALING)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: unknown flag bits in %d", flags);
+    if (flags && Cin != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: the input transforms are for Cin = 3 (got %d)", Cin);
+    GSR_HIP(lpips_launch_conv(B, Cin, Cout, H, W, in, weights_packed, bias, out, flags, (hipStream_t)stream), "conv3x3");
+    return GSR_OK;
+}
+
 // ---- render_set's output frames (frames.hip) ----
 static int frames_check_sizes(const char* what, int B, int H, int W)
 {

@@ -494,6 +494,17 @@ hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const f
                           long long mask_stride_c, int flags, const double taps[3] /* g_0, g_1, g_2 of the window */, void* workspace,
                           double* sums, float* metrics, hipStream_t stream);
 
+// lpips.hip: conv3x3 + bias + ReLU on the f32 matrix cores and the LPIPS chain (validated by the caller).  The packed weights of a layer
+// are [Cout / LPIPS_CONV_NB][ceil(Cin / LPIPS_CONV_KC)][9][LPIPS_CONV_KC][LPIPS_CONV_NB] floats, zero where the channel is beyond Cin.
+#define LPIPS_CONV_KC 8
+#define LPIPS_CONV_NB 64
+hipError_t lpips_launch_conv(int N, int Cin, int Cout, int H, int W, const float* in, const float* wpack, const float* bias, float* out, int flags,
+                             hipStream_t stream);
+size_t lpips_workspace_bytes(int B, int H, int W);
+hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
+                        const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
+                        float* out_layers, float* out_masked, float* out_spatial, hipStream_t stream);
+
 // frames.hip: render_set's output frames (validated by the caller).  Stats: one workgroup per FRAME_STATS_CHUNK elements of a frame writes
 // eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}: the workspace is B*chunks*8 doubles, used again by the second pass (lo2 / hi2).
 // Compose: `dwords` = whole-dword stores (the caller has checked out's alignment and channels_out == 4 or W_out % 4 == 0).

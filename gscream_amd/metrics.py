@@ -299,21 +299,29 @@ def _stack_masks(masks):
     return torch.cat([m.expand(-1, channels, -1, -1) for m in four])
 
 
-def evaluate_views(renders, gts, masks=None, image_names=None, quantize=True):
-    """The metric loop of evaluate() (train.py:943-953, :981-987) without LPIPS: lists of equally sized images ([C,H,W] or [1,C,H,W]) and of
+def evaluate_views(renders, gts, masks=None, image_names=None, quantize=True, lpips=None):
+    """The metric loop of evaluate() (train.py:943-953, :981-987), without LPIPS unless a model is passed: lists of equally sized images ([C,H,W] or [1,C,H,W]) and of
     bool masks -> (full, per_view) with the keys "SSIM", "PSNR", "masked SSIM", "masked PSNR": full[key] is the fp32 mean of the fp32
     per-view values, as evaluate() takes it; per_view[key] maps image name to value.  quantize=True applies the PNG round trip that
     lies between render_set and evaluate() to float images (a no-op on images read back from PNG).  One call per 65535 planes, one
-    read-back.  Without masks the masked keys repeat the unmasked values."""
+    read-back.  Without masks the masked keys repeat the unmasked values.  lpips: a gscream_amd.lpips.LPIPS model adds the keys "LPIPS"
+    and "masked LPIPS" (lpips.lpips_views on the images as they are, 2*x-1 applied: train.py:948, :952-953; without masks the masked
+    key is the mean of the spatial map); their values join the one read-back.  Without it the result is exactly the four keys."""
     if len(renders) == 0 or len(renders) != len(gts) or (masks is not None and len(masks) != len(renders)):
         raise ValueError("evaluate_views: renders, gts and masks are non-empty lists of one length")
     names = [str(i) for i in range(len(renders))] if image_names is None else list(image_names)
     if len(names) != len(renders):
         raise ValueError("evaluate_views: one name per view")
     _sums, metrics = _run(_stack(renders), _stack(gts), None if masks is None else _stack_masks(masks), False, quantize)
+    columns = (("SSIM", 3), ("PSNR", 2), ("masked SSIM", 7), ("masked PSNR", 6))
+    if lpips is not None:
+        from . import lpips as _lpips
+        plain, masked = _lpips.lpips_views(lpips, renders, gts, masks)
+        metrics = torch.cat([metrics, plain.to(metrics.device)[:, None], masked.to(metrics.device)[:, None]], 1)
+        columns += (("LPIPS", 8), ("masked LPIPS", 9))
     host = metrics.cpu()  # the one read-back
     full, per_view = {}, {}
-    for key, column in (("SSIM", 3), ("PSNR", 2), ("masked SSIM", 7), ("masked PSNR", 6)):
+    for key, column in columns:
         values = host[:, column].contiguous()
         full[key] = values.mean().item()
         per_view[key] = dict(zip(names, values.tolist()))

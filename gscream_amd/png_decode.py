@@ -318,11 +318,12 @@ def read_images(renders_dir, gt_dir, mask_dir, device="cuda", reader="hip"):
     return renders, gts, names, masks
 
 
-def evaluate_files(renders_dir, gt_dir, mask_dir, device="cuda", reader=None):
-    """read_images, then metrics.evaluate_views: the loop of evaluate() (train.py:905-987) without LPIPS -> (full, per_view).
+def evaluate_files(renders_dir, gt_dir, mask_dir, device="cuda", reader=None, lpips=None):
+    """read_images, then metrics.evaluate_views: the loop of evaluate() (train.py:905-987) -> (full, per_view); without LPIPS unless
+    `lpips` is a gscream_amd.lpips.LPIPS model, which adds the keys "LPIPS" and "masked LPIPS".
     reader: "hip" or "pil"; None takes the module's measured default (INTEGRATION V)."""
     from . import metrics
     if reader is None:
         reader = "pil" if use_pil_in_evaluate_files else "hip"
     renders, gts, names, masks = read_images(renders_dir, gt_dir, mask_dir, device, reader)
-    return metrics.evaluate_views(renders, gts, masks, names)
+    return metrics.evaluate_views(renders, gts, masks, names, lpips=lpips)

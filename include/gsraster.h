@@ -519,6 +519,65 @@ int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float
                       int flags, void* workspace, double* sums /* [B,8] */, float* metrics /* [B,8] */, void* stream /* hipStream_t */);
 
 /*
+ * LPIPS: the third metric evaluate() (train.py:905-987) reports per view, plain (lpips_fn, :948) and masked (the mean of
+ * loss_fn_vgg_spatial's map under the mask, :952-953), from ONE VGG-16 pass over the pair.  This is LPIPS v0.1, net = 'vgg',
+ * lpips = True, eval mode.  in0, in1 are fp32 [B,3,H,W] with H, W >= 16, nominally in [-1, 1].
+ *
+ *   flag NORMALIZE (the package's normalize=True; evaluate() writes 2*x-1 itself):  x := 2x - 1              one fp32 rounding
+ *   scaling layer   x := (x - shift[c]) / scale[c]    shift = (-.030, -.088, -.188)  scale = (.458, .448, .450)
+ *                   one fp32 subtraction and one IEEE fp32 division.  The zero padding of the first convolution is applied AFTER
+ *                   this step: a border tap contributes 0, not (0 - shift) / scale.
+ *   features        13 convolutions, 3x3, stride 1, zero pad 1, bias, ReLU, of widths
+ *                       3->64, 64->64 | 64->128, 128->128 | 128->256, 256->256, 256->256 | 256->512, 512->512, 512->512 |
+ *                       512->512, 512->512, 512->512
+ *                   `|` = 2x2 stride-2 max-pool with floor (an odd last row or column is dropped: 567 -> 283 -> 141 -> 70 -> 35).
+ *                   The taps f_l, l = 0..4, are the ReLU outputs that end the five groups, C_l = 64, 128, 256, 512, 512.
+ *                   Each output element is ONE fp32 fma chain (v_mfma_f32_32x32x2_f32, bit for bit an fmaf chain):
+ *                       acc = bias[co];  for chunk = 0 .. ceil(Cin/8)-1:  for ky = 0..2: for kx = 0..2:  for ci = 8 chunk .. 8 chunk + 7:
+ *                           acc = fma(w[co][ci][ky][kx], x[ci][y+ky-1][x+kx-1], acc)
+ *                   (the bias is the start value of the chain; channels ci >= Cin of the last chunk are fma(0, 0, acc) = acc);
+ *                   out = acc < 0 ? 0 : acc.  The order is the same for every element: the same inputs give the same bits.
+ *   head, per tap   n = sqrt(sum_c f^2) for both images;  fh = f / (n + 1e-10);  d_c = (fh0_c - fh1_c)^2;
+ *                   m_l[y,x] = sum_c lin_l[c] d_c   (the bias-free 1x1 `lin` convolution; dropout is the identity)
+ *                   every step in fp64 on the fp32 features, the channel sums in ascending c, no contraction; m_l is stored
+ *                   rounded to fp32 once (the spatial map reads that), its fp64 value enters the plain sums
+ *   out_layers[b,l] = mean_{y,x} m_l        out_plain[b] = sum_l mean_l       spatial sums and the sum over l in fp64, in a fixed order
+ *                   without atomics; each rounded to fp32 once
+ *   out_spatial[b,y,x] = sum_l bilinear_l(m_l)[y,x]  at H x W, fp32, one rounding per operation, the taps added in ascending l.
+ *                   torch's Upsample(size=(H,W), mode='bilinear', align_corners=False):  scale = in / out;
+ *                   src = max(scale (dst + 0.5) - 0.5, 0);  i0 = trunc(src);  i1 = min(i0 + 1, in - 1);  t = src - i0;
+ *                   value = (1-ty) ((1-tx) v00 + tx v01) + ty ((1-tx) v10 + tx v11)
+ *   out_masked[b]   = the mean of out_spatial[b] over the pixels where mask (bytes, 0 = false, read through
+ *                   mask + b*mask_stride_b + y*W + x; stride 0 = one mask for all views; NULL = every pixel) is true; the sum and
+ *                   the count in fp64, the quotient rounded to fp32.  An empty mask gives NaN (0/0), as torch's mean does.
+ *
+ * The rule is pinned AS WRITTEN ABOVE ONLY: neither the lpips package nor torchvision nor any VGG / LPIPS weights are on this
+ * stack, so no run of the package stands behind it.  The caller brings the weights:
+ *   conv_weights  the 13 layers in order, each packed [Cout/64][ceil(Cin/8)][9 = ky*3+kx][8 = ci % 8][64 = co % 64] with zeros where
+ *                 ci >= Cin (14 713 344 floats: the sum over the layers of (Cout/64) * ceil(Cin/8) * 4608)
+ *   conv_bias     the 13 biases in order (4224 floats)         lin_weights   the five lin vectors in order (1472 floats)
+ * workspace: gsr_lpips_workspace_bytes(B, H, W) bytes (0 for sizes the call rejects; two activation buffers of 2B*64*H*W floats,
+ * the five maps and the partial sums), written before it is read.  out_layers [B,5], out_masked [B] and out_spatial [B,H,W] may be
+ * NULL.  The call launches on `stream`, never synchronises and reads nothing back.  Rejected before launching
+ * (GSR_ERR_INVALID_ARGUMENT, text in gsr_last_error): B outside 1 .. 32767; H or W < 16; H*W >= 2^31 - 256; NULL in0, in1,
+ * conv_weights, conv_bias, lin_weights, workspace or out_plain; flag bits other than NORMALIZE; a negative mask stride.
+ *
+ * gsr_conv3x3_relu is one layer of the chain on its own: in [B,Cin,H,W] -> out [B,Cout,H,W], Cout a multiple of 64, weights packed
+ * as above.  flags NORMALIZE and SCALING (Cin = 3 only) apply the two input steps to the pixels inside the image.  Rejected before
+ * launching: B outside 1 .. 65535; Cin <= 0; Cout no positive multiple of 64; Cin or Cout > 65536; H or W <= 0; H*W >= 2^31 - 256;
+ * a NULL pointer; unknown flag bits; flags with Cin != 3.
+ */
+#define GSR_LPIPS_NORMALIZE 1
+#define GSR_LPIPS_SCALING   2
+size_t gsr_lpips_workspace_bytes(int B, int H, int W);
+int gsr_lpips(int B, int H, int W, const float* in0 /* [B,3,H,W] */, const float* in1, int flags, const float* conv_weights,
+              const float* conv_bias, const float* lin_weights, const uint8_t* mask /* or NULL */, long long mask_stride_b,
+              void* workspace, float* out_plain /* [B] */, float* out_layers /* [B,5] or NULL */, float* out_masked /* [B] or NULL */,
+              float* out_spatial /* [B,H,W] or NULL */, void* stream /* hipStream_t */);
+int gsr_conv3x3_relu(int B, int Cin, int Cout, int H, int W, const float* in, const float* weights_packed, const float* bias,
+                     float* out, int flags, void* stream /* hipStream_t */);
+
+/*
  * Output frames: what render_set (train.py:710-848) does between the render and the PNG encoder -- save_image's quantisation, the
  * error map, the normal picture's second normalisation, the least-squares depth alignment of compute_scale_and_shift (:198-218), the
  * two colour maps (cv2.applyColorMap for the spiral video, plt.imsave for the train / test sets), the flips, the one-channel expand
