@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "gsr_png_decode_workspace_bytes", "gsr_png_decode",
     "gsr_sort_block_keys", "gsr_sort_keys_workspace_bytes", "gsr_sort_keys_u64", "gsr_voxelize_workspace_bytes", "gsr_voxelize",
     "gsr_kth_smallest_workspace_bytes", "gsr_kth_smallest_f32", "gsr_scene_init_fill",
+    "gsr_resize_u8", "gsr_resize_f32", "gsr_resize_nearest_u8", "gsr_resize_nearest_f32",
 )
 NUM_STAGES = 7
 ABI_VERSION = 8  # include/gsraster.h GSR_ABI_VERSION this binding was written against
@@ -84,6 +85,8 @@ PNG_PIECE_IDAT, PNG_PIECE_START = 1, 2
 PNG_STATUS = ("ok", "truncated", "reserved block type", "stored LEN/NLEN mismatch", "over-subscribed or incomplete code", "invalid symbol",
               "distance before the start of the stream", "stream longer than the picture's", "stream shorter than the picture's",
               "filter byte above 4", "Adler-32 mismatch", "CRC-32 mismatch", "table entry out of bounds")  # GSR_PNG_OK .. GSR_PNG_TABLE
+RESIZE_HORIZONTAL, RESIZE_VERTICAL = 0, 1  # GSR_RESIZE_* of include/gsraster.h
+RESIZE_U8, RESIZE_DIV255, RESIZE_GT0 = range(3)
 FRAME_QUANT, FRAME_QUANT_CLAMP, FRAME_ABSDIFF, FRAME_NORMAL, FRAME_CMAP_CV, FRAME_CMAP_MPL_ALIGNED, FRAME_CMAP_MPL = range(7)
 
 
@@ -257,6 +260,15 @@ def load():
     lib.gsr_kth_smallest_f32.argtypes = [_c_int, _c_int] + [_vp] * 4
     lib.gsr_scene_init_fill.restype = _c_int
     lib.gsr_scene_init_fill.argtypes = [_c_int] * 3 + [_vp, _vp, _c_float] + [_vp] * 9
+    _ll = ctypes.c_longlong
+    lib.gsr_resize_u8.restype = _c_int
+    lib.gsr_resize_u8.argtypes = [_vp, _ll, _ll] + [_c_int] * 6 + [_vp, _vp, _c_int, _vp, _ll, _ll, _c_int, _vp]
+    lib.gsr_resize_f32.restype = _c_int
+    lib.gsr_resize_f32.argtypes = [_vp, _ll, _ll] + [_c_int] * 5 + [_vp, _vp, _c_int, _vp, _ll, _ll, _vp]
+    lib.gsr_resize_nearest_u8.restype = _c_int
+    lib.gsr_resize_nearest_u8.argtypes = [_vp, _ll, _ll] + [_c_int] * 6 + [_vp, _vp, _vp, _ll, _ll, _c_int, _vp]
+    lib.gsr_resize_nearest_f32.restype = _c_int
+    lib.gsr_resize_nearest_f32.argtypes = [_vp, _ll, _ll] + [_c_int] * 5 + [_vp, _vp, _vp, _ll, _ll, _vp]
     _lib = lib
     return lib
 

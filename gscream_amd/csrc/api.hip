@@ -1344,3 +1344,90 @@ extern "C" int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png
             "png decode");
     return GSR_OK;
 }
+
+// ---- resize (resize.hip) ----
+static int resize_check(const char* what, const void* src, const void* out, long long src_image_stride, long long src_row_stride, int n, int H, int W,
+                        int C, int H_out, int W_out, long long out_image_stride, long long out_row_stride, int epilogue)
+{
+    if (!src || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: src or out is NULL", what);
+    if (n < 1 || H < 1 || W < 1 || H_out < 1 || W_out < 1)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: n, H, W and the output sizes must be >= 1 (got %d, %d x %d -> %d x %d)", what, n, H, W, H_out, W_out);
+    if (C < 1 || C > 4) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: C=%d (need 1 .. 4)", what, C);
+    if (n > 65535 || H > 65535 || W > 65535 || H_out > 65535 || W_out > 65535)
+        return gsr_fail(GSR_ERR_UNSUPPORTED, "%s: n, H, W and the output sizes are at most 65535", what);
+    if (epilogue != GSR_RESIZE_U8 && epilogue != GSR_RESIZE_DIV255 && epilogue != GSR_RESIZE_GT0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: epilogue=%d", what, epilogue);
+    if (src_row_stride < (long long)W * C || (n > 1 && src_image_stride < (long long)(H - 1) * src_row_stride + (long long)W * C))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: source strides %lld / %lld are below the row or the picture", what, src_image_stride, src_row_stride);
+    if (epilogue == GSR_RESIZE_U8) {
+        if (out_row_stride < (long long)W_out * C || (n > 1 && out_image_stride < (long long)(H_out - 1) * out_row_stride + (long long)W_out * C))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: output strides %lld / %lld are below the row or the picture", what, out_image_stride, out_row_stride);
+    } else if (out_row_stride != W_out || out_image_stride != (long long)C * H_out * W_out) {
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the float forms are contiguous [n][C][H'][W'] (strides %lld / %lld)", what, out_image_stride, out_row_stride);
+    }
+    return GSR_OK;
+}
+
+static int resize_check_pass(const char* what, int axis, int out_len, const void* bounds, const void* coeffs, int ksize)
+{
+    if (axis != GSR_RESIZE_HORIZONTAL && axis != GSR_RESIZE_VERTICAL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: axis=%d", what, axis);
+    if (!bounds || !coeffs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bounds or coeffs is NULL", what);
+    if (ksize < 1 || out_len < 1 || (long long)out_len * ksize > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: ksize=%d, out_len=%d", what, ksize, out_len);
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis, int out_len,
+                             const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride, long long out_row_stride,
+                             int epilogue, void* stream)
+{
+    if (int rc = resize_check_pass("resize_u8", axis, out_len, bounds, coeffs, ksize)) return rc;
+    const int H_out = axis == GSR_RESIZE_VERTICAL ? out_len : H, W_out = axis == GSR_RESIZE_VERTICAL ? W : out_len;
+    if (int rc = resize_check("resize_u8", src, out, src_image_stride, src_row_stride, n, H, W, C, H_out, W_out, out_image_stride, out_row_stride, epilogue))
+        return rc;
+    GSR_HIP(resize_launch_u8(src, src_image_stride, src_row_stride, n, H, W, C, axis, out_len, bounds, coeffs, ksize, out, out_image_stride,
+                             out_row_stride, epilogue, (hipStream_t)stream), "resize_u8");
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
+                              const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride, long long out_row_stride,
+                              void* stream)
+{
+    if (int rc = resize_check_pass("resize_f32", axis, out_len, bounds, coeffs, ksize)) return rc;
+    const int H_out = axis == GSR_RESIZE_VERTICAL ? out_len : H, W_out = axis == GSR_RESIZE_VERTICAL ? W : out_len;
+    if (int rc = resize_check("resize_f32", src, out, src_image_stride, src_row_stride, n, H, W, 1, H_out, W_out, out_image_stride, out_row_stride,
+                              GSR_RESIZE_U8))
+        return rc;
+    GSR_HIP(resize_launch_f32(src, src_image_stride, src_row_stride, n, H, W, axis, out_len, bounds, coeffs, ksize, out, out_image_stride,
+                              out_row_stride, (hipStream_t)stream), "resize_f32");
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_nearest_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int H_out,
+                                     int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
+                                     long long out_row_stride, int epilogue, void* stream)
+{
+    if (int rc = resize_check("resize_nearest_u8", src, out, src_image_stride, src_row_stride, n, H, W, C, H_out, W_out, out_image_stride,
+                              out_row_stride, epilogue))
+        return rc;
+    if ((!yidx && H_out != H) || (!xidx && W_out != W))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "resize_nearest_u8: a NULL index table is the identity and needs equal sizes");
+    GSR_HIP(resize_launch_nearest(src, src_image_stride, src_row_stride, n, H, W, C, 0, H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride,
+                                  epilogue, (hipStream_t)stream), "resize_nearest_u8");
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_nearest_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int H_out, int W_out,
+                                      const int32_t* yidx, const int32_t* xidx, float* out, long long out_image_stride, long long out_row_stride,
+                                      void* stream)
+{
+    if (int rc = resize_check("resize_nearest_f32", src, out, src_image_stride, src_row_stride, n, H, W, 1, H_out, W_out, out_image_stride,
+                              out_row_stride, GSR_RESIZE_U8))
+        return rc;
+    if ((!yidx && H_out != H) || (!xidx && W_out != W))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "resize_nearest_f32: a NULL index table is the identity and needs equal sizes");
+    GSR_HIP(resize_launch_nearest(src, src_image_stride, src_row_stride, n, H, W, 1, 1, H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride,
+                                  GSR_RESIZE_U8, (hipStream_t)stream), "resize_nearest_f32");
+    return GSR_OK;
+}

@@ -533,3 +533,14 @@ size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces);
 hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                              hipStream_t stream);
+
+// resize.hip: PIL's Image.resize, one pass (or one NEAREST gather) per launch (validated by the caller)
+hipError_t resize_launch_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis,
+                            int out_len, const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride,
+                            long long out_row_stride, int epilogue, hipStream_t stream);
+hipError_t resize_launch_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
+                             const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride,
+                             long long out_row_stride, hipStream_t stream);
+hipError_t resize_launch_nearest(const void* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int is_f32,
+                                 int H_out, int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
+                                 long long out_row_stride, int epilogue, hipStream_t stream);

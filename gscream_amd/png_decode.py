@@ -35,7 +35,7 @@ __all__ = ["PngError", "PngPictures", "check", "decode", "evaluate_files", "pars
 
 force_torch = False
 last_path = None  # "hip" / "torch": the path the last decode took
-last_info = {}    # filled by check / read / read_images: files, segments, parallel, serial, host_decoded, masks_resized
+last_info = {}    # filled by check / read / read_images: files, segments, parallel, serial, host_decoded, masks_resized (read_images: masks_resized_hip)
 use_pil_in_evaluate_files = True  # measured (tools/png_decode_bench.py, INTEGRATION V): the 80-file batch does not beat PIL's loop
 
 _SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -277,13 +277,16 @@ def _to_float(image):
     return (image.permute(2, 0, 1)[None, :3].to(torch.float32) / 255.0)
 
 
-def read_images(renders_dir, gt_dir, mask_dir, device="cuda", reader="hip"):
+def read_images(renders_dir, gt_dir, mask_dir, device="cuda", reader="hip", mask_resize="pil"):
     """readImages (train.py:887-902): -> (renders, gts, image_names, masks).  renders and gts are fp32 [1, 3, H, W] (uint8 / 255, the
     first three channels), image_names the file names of renders_dir in os.listdir order, masks bool [1, 3, H, W] (> 0, the channel
     dimension an expand, not materialised).  The mask of `name` is mask_dir/out_%05d.png with the index 1 + int(stem).  All files go to
     the device in one decode.  A mask whose size differs from its render's takes the reference's own
     mask.resize((W, H), Image.LANCZOS) on the host before upload (the reference resizes every mask to 1008 x 567, its render size);
-    last_info["masks_resized"] counts them.  reader="pil" reads every file with PIL instead (the reference's way)."""
+    last_info["masks_resized"] counts them.  reader="pil" reads every file with PIL instead (the reference's way).
+    mask_resize="hip" resizes the mask this call has already decoded on the device instead (gscream_amd.resize, LANCZOS, the same
+    bytes), when it has one or three channels; a mask with an alpha channel (PNG colour types 4 and 6: PIL premultiplies) and a
+    host-decoded file keep the PIL call.  last_info["masks_resized_hip"] counts the device ones among masks_resized."""
     global last_info
     from PIL import Image
     names = list(os.listdir(renders_dir))
@@ -293,6 +296,8 @@ def read_images(renders_dir, gt_dir, mask_dir, device="cuda", reader="hip"):
     gp = [os.path.join(gt_dir, n) for n in names]
     mp = [os.path.join(mask_dir, "out_%05d.png" % (1 + int(n.split(".")[0]))) for n in names]
     device = torch.device(device)
+    if mask_resize not in ("pil", "hip"):
+        raise ValueError(f"png_decode: mask_resize={mask_resize!r} (have 'pil', 'hip')")
     if reader == "pil":
         images = [torch.from_numpy(_pil_picture(open(p, "rb").read())).to(device) for p in rp + gp + mp]
         info = {"files": len(images), "segments": 0, "parallel": 0, "serial": 0, "host_decoded": len(images), "masks_resized": 0}
@@ -303,27 +308,36 @@ def read_images(renders_dir, gt_dir, mask_dir, device="cuda", reader="hip"):
         raise ValueError(f"png_decode: reader={reader!r} (have 'hip', 'pil')")
     k = len(names)
     renders, gts, masks = [_to_float(t) for t in images[:k]], [_to_float(t) for t in images[k:2 * k]], []
-    resized = 0
+    resized = resized_hip = 0
     for i, m in enumerate(images[2 * k:]):
         H, W = renders[i].shape[2:]
         if tuple(m.shape[:2]) != (H, W):
             resized += 1
-            small = np.asarray(Image.open(mp[i]).resize((W, H), Image.LANCZOS))
-            m = torch.from_numpy(np.ascontiguousarray(small.reshape(H, W, -1))).to(device)
+            if mask_resize == "hip" and reader == "hip" and m.is_cuda and m.shape[2] in (1, 3):
+                from . import resize as _resize
+                m = _resize.resize(m, (W, H), _resize.LANCZOS)
+                resized_hip += _resize.last_path == "hip"
+            else:
+                small = np.asarray(Image.open(mp[i]).resize((W, H), Image.LANCZOS))
+                m = torch.from_numpy(np.ascontiguousarray(small.reshape(H, W, -1))).to(device)
         if m.dtype != torch.uint8 or m.shape[2] != 1:
+            info["masks_resized"], info["masks_resized_hip"] = resized, int(resized_hip)
+            last_info = info  # (the counts up to the mask that is refused)
             raise ValueError(f"png_decode: mask {mp[i]} has {m.shape[2]} channels (readImages expands one channel to three)")
         masks.append((m.permute(2, 0, 1) > 0).expand(3, -1, -1)[None])
     info["masks_resized"] = resized
+    info["masks_resized_hip"] = int(resized_hip)
     last_info = info
     return renders, gts, names, masks
 
 
-def evaluate_files(renders_dir, gt_dir, mask_dir, device="cuda", reader=None, lpips=None):
+def evaluate_files(renders_dir, gt_dir, mask_dir, device="cuda", reader=None, lpips=None, mask_resize=None):
     """read_images, then metrics.evaluate_views: the loop of evaluate() (train.py:905-987) -> (full, per_view); without LPIPS unless
     `lpips` is a gscream_amd.lpips.LPIPS model, which adds the keys "LPIPS" and "masked LPIPS".
-    reader: "hip" or "pil"; None takes the module's measured default (INTEGRATION V)."""
+    reader: "hip" or "pil"; None takes the module's measured default (INTEGRATION V).  mask_resize: "pil" or "hip" as in read_images;
+    None is "pil" (INTEGRATION X has the measurement)."""
     from . import metrics
     if reader is None:
         reader = "pil" if use_pil_in_evaluate_files else "hip"
-    renders, gts, names, masks = read_images(renders_dir, gt_dir, mask_dir, device, reader)
+    renders, gts, names, masks = read_images(renders_dir, gt_dir, mask_dir, device, reader, "pil" if mask_resize is None else mask_resize)
     return metrics.evaluate_views(renders, gts, masks, names, lpips=lpips)

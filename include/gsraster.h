@@ -782,6 +782,56 @@ int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* file
                    void* stream /* hipStream_t */);
 
 /*
+ * ---- Resize (resize.hip): PIL's Image.resize, byte for byte for 8-bit pictures and bit for bit for mode F ---------------------
+ * Replaces mask.resize((1008, 567), Image.LANCZOS) of readImages (train.py:887-902) and pil_image.resize(resolution) of the
+ * PILtoTorch* functions (utils/general_utils.py:35-75; PIL's default filter, BICUBIC) with their last step: / 255.0, > 0, or nothing.
+ *
+ * The rule, along one axis, inS -> outS, for a filter f of support s (BOX 0.5, BILINEAR 1, BICUBIC 2 with a = -0.5, LANCZOS 3):
+ *   tables   (host, double; gscream_amd/resize.py)  scale = inS / outS, fs = max(scale, 1), support = s fs, ksize = ceil(support) 2 + 1;
+ *            per output xx: c = (xx + 0.5) scale, xmin = max(int(c - support + 0.5), 0), n = min(int(c + support + 0.5), inS) - xmin,
+ *            w[x] = f((x + xmin - c + 0.5) (1 / fs)), ww = their sum in index order, k[x] = w[x] / ww where ww != 0.
+ *            bounds: int32 [outS][2] = {xmin, n};  coeffs: [outS][ksize], zero behind n.
+ *   8-bit    coeffs int32 K = trunc(k 2^22 +- 0.5) (the sign of k);  acc = 2^21 + sum src[xmin + x] K[x] in int32 per channel;
+ *            out = clamp(acc >> 22, 0, 255), the shift arithmetic.  Channels are independent.
+ *   float32  coeffs double;  ss = 0, ss += double(src[xmin + x]) k[x] for x < n in index order, one rounding per operation, every
+ *            tap of the bound included (0 * inf = NaN);  out = float(ss).
+ *   passes   PIL runs the horizontal pass where the widths differ, then the vertical pass on its result where the heights differ;
+ *            the intermediate is rounded to the picture's own type.  One call here is one pass: axis GSR_RESIZE_HORIZONTAL resamples
+ *            W -> out_len in every row, GSR_RESIZE_VERTICAL resamples H -> out_len in every column.
+ *   NEAREST  out[y][x] = src[yidx[y]][xidx[x]];  the tables are PIL's accumulated xo = 0.5 a, xo += a, index int(xo) (host).
+ *            A NULL table is the identity, so equal sizes run an epilogue alone.
+ * The kernels clip a bound to its row again (xmin >= 0, n <= inS - xmin, n <= ksize) and an index to [0, inS - 1]: no table takes a
+ * load outside the picture.
+ *
+ * src: n pictures of H x W pixels of C interleaved channels (8-bit: C = 1 .. 4; float32: one channel), the channels of a pixel and
+ * the pixels of a row adjacent, rows src_row_stride and pictures src_image_stride ELEMENTS apart (>= W C; a view of a wider tensor).
+ * out, by `epilogue` (8-bit only):
+ *   GSR_RESIZE_U8      uint8 [n][H'][W'][C], rows out_row_stride and pictures out_image_stride bytes apart
+ *   GSR_RESIZE_DIV255  float32 [n][C][H'][W'] contiguous = __fdiv_rn(float(v), 255.0f): PILtoTorch's `/ 255.0` and permute
+ *   GSR_RESIZE_GT0     float32 [n][C][H'][W'] contiguous = v > 0 ? 1 : 0: PILtoTorch_01mask's
+ *   (for the float forms out_row_stride = W' and out_image_stride = C H' W' are required).
+ * gsr_resize_f32 writes float32 [n][H'][W'] with the two strides in elements.
+ * All pointers are device pointers; the calls launch one kernel on `stream`, allocate nothing, never synchronise, read nothing
+ * back.  Rejected before launching: NULL pointers, sizes < 1, C outside 1 .. 4, H, W, out sizes or n above 65535, ksize < 1,
+ * strides below the row or picture they step over, an unknown axis or epilogue.
+ */
+#define GSR_RESIZE_PRECISION_BITS 22
+enum { GSR_RESIZE_HORIZONTAL = 0, GSR_RESIZE_VERTICAL = 1 };
+enum { GSR_RESIZE_U8 = 0, GSR_RESIZE_DIV255 = 1, GSR_RESIZE_GT0 = 2 };
+int gsr_resize_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis, int out_len,
+                  const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride, long long out_row_stride,
+                  int epilogue, void* stream /* hipStream_t */);
+int gsr_resize_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
+                   const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride, long long out_row_stride,
+                   void* stream /* hipStream_t */);
+int gsr_resize_nearest_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int H_out, int W_out,
+                          const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride, long long out_row_stride, int epilogue,
+                          void* stream /* hipStream_t */);
+int gsr_resize_nearest_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int H_out, int W_out,
+                           const int32_t* yidx, const int32_t* xidx, float* out, long long out_image_stride, long long out_row_stride,
+                           void* stream /* hipStream_t */);
+
+/*
  * ---- the image-space RGB loss that follows the rasterizer ----------------------------------
  * Fused weighted L1 + weighted SSIM (11x11 Gaussian window, sigma 1.5, zero padding), value and gradient:
  *     L = a_l1 * mean(|img - gt| * m) + a_ssim * mean(ssim_map(img, gt) * m),   m = weight[H,W] (1 when NULL),
