@@ -299,9 +299,13 @@ def check(rc, what):
 
 
 def ptr(t):
-    """Device pointer of a tensor, or NULL for None / empty tensors (the reference's 'not provided')."""
+    """Device pointer of a tensor, or NULL for None / empty tensors (the reference's 'not provided').  A tensor in host memory
+    raises: the native entry points do not look at their pointers, so a kernel handed one faults instead of failing."""
     if t is None or t.numel() == 0:
         return None
+    if not t.is_cuda:
+        raise RuntimeError(f"gscream_amd: a {t.device} tensor ({tuple(t.shape)}, {t.dtype}) was about to be passed to a HIP kernel; "
+                           "move it to the device first (the kernels do not check their pointers)")
     return ctypes.c_void_p(t.data_ptr())
 
 
@@ -337,6 +341,9 @@ class on_device:
 
 def run(name, device, *args):
     """lib.<name>(*args, stream) with `device` (a tensor's) current and on its current stream; raises unless it returns 0.
-    The caller keeps every tensor behind `args` referenced until this returns (the launches are then enqueued)."""
+    The caller keeps every tensor behind `args` referenced until this returns (the launches are then enqueued).  A tensor among
+    `args` is passed as ptr(tensor): its device is checked here, at the launch."""
+    if any(isinstance(a, torch.Tensor) for a in args):
+        args = [ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
     with on_device(device.index) as index:
         check(getattr(load(), name)(*args, ctypes.c_void_p(stream_handle(index))), name)

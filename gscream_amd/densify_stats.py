@@ -23,22 +23,24 @@ def training_statis(model, viewspace_point_tensor, opacity, update_filter, offse
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("the accumulators must be contiguous float32 tensors (they are updated in place)")
     dev = acc.device
-    uf = update_filter.detach().reshape(-1)
+    # masks and the gradient may arrive in host memory (the reference indexes device accumulators with whatever it is given)
+    update_filter, offset_selection_mask_d = update_filter.detach().to(dev), offset_selection_mask.detach().to(dev)
+    uf = update_filter.reshape(-1)
     uf = (uf if uf.dtype == torch.uint8 else uf.view(torch.uint8) if uf.dtype == torch.bool else uf.to(torch.uint8)).contiguous()
-    grad = viewspace_point_tensor.grad.detach().contiguous().float()
+    grad = viewspace_point_tensor.grad.detach().to(dev).contiguous().float()
     M = int(uf.shape[0])
     if M != int(grad.shape[0]):
         raise ValueError("update_filter and viewspace_point_tensor.grad disagree on the number of Gaussians")
-    sel = offset_selection_mask.detach().reshape(-1)
+    sel = offset_selection_mask_d.reshape(-1)
     sel = (sel if sel.dtype == torch.uint8 else sel.view(torch.uint8) if sel.dtype == torch.bool else sel.to(torch.uint8)).contiguous()
-    nop = opacity.detach().reshape(-1).contiguous().float()
+    nop = opacity.detach().to(dev).reshape(-1).contiguous().float()
     book = getattr(offset_selection_mask, "_gsr_decode", None)
     if book is not None and book.matches(anchor_visible_mask, K) and sel.numel() == book.N * K:
         # the selection mask is the one this package's decode returned for this very visibility mask: its bookkeeping (row
         # list of the visible anchors, first output row per anchor, rows kept) is reused -- no torch kernels, no host sync
         vis, first, Nv, kept = book.vis, book.first, book.N, book.M
     else:
-        vis = torch.nonzero(anchor_visible_mask, as_tuple=False).view(-1).int()
+        vis = torch.nonzero(anchor_visible_mask.detach().to(dev), as_tuple=False).view(-1).int()
         Nv = int(vis.shape[0])
         if sel.numel() != Nv * K:
             raise ValueError(f"offset_selection_mask has {sel.numel()} entries, expected visible anchors * n_offsets = {Nv * K}")

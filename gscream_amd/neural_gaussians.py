@@ -46,10 +46,13 @@ class _Decode(torch.autograd.Function):
             raise IndexError(f"The shape of the mask {list(vis_mask.shape)} at index 0 does not match the shape of the indexed "
                              f"tensor {list(anchor.shape)} at index 0")
         N = int(anchor.shape[0]) if vis_idx is None else int(vis_idx.shape[0])  # anchors decoded (device_rows: the upper bound)
-        vis = None if vis_idx is None else vis_idx.detach().contiguous().int()
         if feat.shape[1] != 32:
             raise NotImplementedError("feat_dim must be 32 (arguments/__init__.py:50)")
         dev = feat.device
+        # the row list and the mask may arrive in host memory (x[mask] takes a CPU mask for a device tensor): the kernels read them
+        vis = None if vis_idx is None else vis_idx.detach().to(dev).contiguous().int()
+        if vis_mask is not None:
+            vis_mask = vis_mask.detach().to(dev)
         f32 = lambda t: t.detach().contiguous().float()
         feat_c, anchor_c, off_c, gs_c, cam_c = f32(feat), f32(anchor), f32(offsets), f32(gscale), f32(campos)
         ws = [f32(w) for w in weights]
@@ -63,7 +66,7 @@ class _Decode(torch.autograd.Function):
             scratch = torch.empty((N // 256 + 2,), dtype=torch.int32, device=dev)
             vis_count = None
             if device_rows:
-                vmask8 = vis_mask.detach().contiguous().view(torch.uint8)
+                vmask8 = vis_mask.contiguous().view(torch.uint8)
                 vis = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
                 vis_count = total[1:]
                 _native.run("gsr_decode_visible_rows", dev, N, _native.ptr(vmask8), _native.ptr(vis), _native.ptr(vis_count), _native.ptr(scratch))
@@ -93,7 +96,7 @@ class _Decode(torch.autograd.Function):
         # the boolean mask the row list came from (one byte per model row), if the caller has it: lets the backward zero the hidden
         # rows only instead of zero-filling the model-sized gradients.  Saved through autograd, whose version check turns an in-place
         # change of the mask between forward and backward into an error instead of wrong zeros.
-        vmask_saved = None if (vis is None or vis_mask is None) else vis_mask.detach().contiguous().view(torch.uint8)
+        vmask_saved = None if (vis is None or vis_mask is None) else vis_mask.contiguous().view(torch.uint8)
         ctx.has_vis_mask = vmask_saved is not None
         ctx.save_for_backward(feat_c, anchor_c, off_c, gs_c, cam_c, mask, first, *ws, *([vmask_saved] if vmask_saved is not None else []))
         ctx.vis = vis
@@ -260,14 +263,39 @@ def _generate_with_feature_bank(viewpoint_camera, pc, visible_mask, is_training)
     return out if is_training else out[:6]
 
 
+def _row_list(rows, n):
+    """An integer index tensor as the decode's row list.  The backward writes each listed row once, so the list must be strictly
+    ascending (what torch.nonzero of a mask gives); x[rows] would also take repeats and any order, which the kernels do not."""
+    if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 1:  # (what torch indexing takes)
+        raise IndexError(f"visible_mask must be a boolean mask or a 1-D integer index tensor, got {rows.dtype} {list(rows.shape)}")
+    if rows.numel():
+        r = rows.detach().long()
+        if int(r[0]) < 0 or int(r[-1]) >= n:
+            raise IndexError(f"index out of range for {n} anchors")
+        if rows.numel() > 1 and not bool((r[1:] > r[:-1]).all()):
+            raise NotImplementedError("an index tensor of visible anchors must be strictly ascending (no repeats)")
+    return rows.detach().int()
+
+
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False):
+    """`visible_mask`: what the reference's `x[visible_mask]` takes -- a boolean mask (on the device: compacted there; in host memory:
+    one torch.nonzero on the host) or an int32 / int64 index tensor on either device.  One deviation: an index tensor must list its rows
+    strictly ascending without repeats (x[rows] also takes any order and repeats; the backward here writes each listed row once), and
+    checking that costs a device index list two host syncs.  Anything else raises."""
     if getattr(pc, "use_feat_bank", False):
         return _generate_with_feature_bank(viewpoint_camera, pc, visible_mask, is_training)
     # gaussian_renderer/__init__.py:20-28: `x[visible_mask]` for four tensors.  Here the mask becomes a row list once
     # and the kernels read (and, in the backward, write) the model-sized tensors through it; no mask = every row.
-    on_device = visible_mask is not None and visible_mask.dtype == torch.bool and visible_mask.is_cuda and visible_mask.dim() == 1
-    # (a boolean mask on the device is compacted there; anything else -- index tensors, CPU masks -- takes the host's nonzero)
-    vis_idx = None if (visible_mask is None or on_device) else torch.nonzero(visible_mask, as_tuple=False).view(-1).int()
+    is_mask = visible_mask is not None and visible_mask.dtype in (torch.bool, torch.uint8)
+    on_device = is_mask and visible_mask.dtype == torch.bool and visible_mask.is_cuda and visible_mask.dim() == 1
+    # (a boolean mask on the device is compacted there; a CPU mask takes the host's nonzero; an integer tensor is the row list itself,
+    # as in x[rows])
+    if visible_mask is None or on_device:
+        vis_idx = None
+    elif is_mask:
+        vis_idx = torch.nonzero(visible_mask, as_tuple=False).view(-1).int()
+    else:
+        vis_idx = _row_list(visible_mask, int(pc.get_anchor.shape[0]))
     _last_decode.clear()
     xyz, color, opacity, uncertainty, scaling, rot, neural_opacity, mask = decode(
         pc._anchor_feat, pc.get_anchor, pc._offset, pc.get_scaling, viewpoint_camera.camera_center, pc.get_opacity_mlp,

@@ -177,8 +177,13 @@ def _f32c(t, device=None):
 
 
 def _p(t):
-    """device address for the C ABI: None (NULL) for absent / empty tensors (the reference's 'not provided')"""
-    return t.data_ptr() if (t is not None and t.numel() != 0) else None
+    """device address for the C ABI: None (NULL) for absent / empty tensors (the reference's 'not provided'); a tensor in host
+    memory raises, in _native.ptr(), the one place that refuses it"""
+    if t is None or t.numel() == 0:
+        return None
+    if not t.is_cuda:
+        _native.ptr(t)
+    return t.data_ptr()
 
 
 def _snapshot(args):
@@ -211,7 +216,7 @@ def _forward_native(means3D, sh, colors_precomp, opacities, uncertainties, scale
     unc, radii = empty((1, H, W), dtype=_F32, device=dev), empty((P,), dtype=torch.int32, device=dev)
 
     # keep every converted tensor referenced until the launches are enqueued
-    means3D_c, opac_c, unc_c = _f32c(means3D), _f32c(opacities), _f32c(uncertainties)
+    means3D_c, opac_c, unc_c = _f32c(means3D), _f32c(opacities, dev), _f32c(uncertainties, dev)  # (all but means3D may arrive in host memory)
     scales_c, rot_c, cov_c = _f32c(scales, dev), _f32c(rotations, dev), _f32c(cov3Ds_precomp, dev)
     colors_c, sh_c = _f32c(colors_precomp, dev), _f32c(sh, dev)
     M = sh_c.shape[1] if (sh_c is not None and sh_c.numel() != 0) else 0
@@ -339,8 +344,8 @@ def _backward_native(rs, num_rendered, binning_capacity, means3D, radii, colors_
     scratch = mk((lib.gsr_backward_scratch_bytes(P, num_rendered),), dtype=torch.uint8, device=dev)
     with _native.on_device(idx):
         rc = lib.gsr_backward(
-            P, int(rs.sh_degree), M, W, H, int(num_rendered), int(binning_capacity), int(max_tile_count), _p(bg), means3D_c.data_ptr(),
-            radii.data_ptr(), _p(colors_c), _p(sh_c), _p(scales_c), float(rs.scale_modifier), _p(rot_c),
+            P, int(rs.sh_degree), M, W, H, int(num_rendered), int(binning_capacity), int(max_tile_count), _p(bg), _p(means3D_c),
+            _p(radii), _p(colors_c), _p(sh_c), _p(scales_c), float(rs.scale_modifier), _p(rot_c),
             _p(cov_c), _p(view), _p(proj), _p(campos), float(rs.tanfovx), float(rs.tanfovy), gc.data_ptr(), _p(gd), _p(gu),
             _p(geom), _p(img), _p(binning), scratch.data_ptr(),
             g_means2D.data_ptr(), g_colors.data_ptr(), g_opac.data_ptr(), g_feat.data_ptr(),

@@ -225,11 +225,11 @@ def _run(x4, size, resample, out4, epilogue):
         yidx = None if H == Ho else _device_tables(device, "nearest", H, Ho, NEAREST)[0]
         xidx = None if W == Wo else _device_tables(device, "nearest", W, Wo, NEAREST)[0]
         if f32:
-            _native.run("gsr_resize_nearest_f32", device, _native.ptr(x4), src_image, src_row, n, H, W, Ho, Wo, _native.ptr(yidx), _native.ptr(xidx),
-                        _native.ptr(out4), out_image, out_row)
+            _native.run("gsr_resize_nearest_f32", device, x4, src_image, src_row, n, H, W, Ho, Wo, yidx, xidx,
+                        out4, out_image, out_row)
         else:
-            _native.run("gsr_resize_nearest_u8", device, _native.ptr(x4), src_image, src_row, n, H, W, C, Ho, Wo, _native.ptr(yidx), _native.ptr(xidx),
-                        _native.ptr(out4), out_image, out_row, epilogue)
+            _native.run("gsr_resize_nearest_u8", device, x4, src_image, src_row, n, H, W, C, Ho, Wo, yidx, xidx,
+                        out4, out_image, out_row, epilogue)
         return 1
     kind = "f32" if f32 else "u8"
     launches = 0
@@ -243,21 +243,21 @@ def _run(x4, size, resample, out4, epilogue):
             dst = torch.empty((n, H, Wo, C), dtype=x4.dtype, device=device)
             dst_image, dst_row, ep = H * Wo * C, Wo * C, _native.RESIZE_U8
         if f32:
-            _native.run("gsr_resize_f32", device, _native.ptr(src), src_image, src_row, n, H, W, _native.RESIZE_HORIZONTAL, Wo, _native.ptr(bounds),
-                        _native.ptr(table), ksize, _native.ptr(dst), dst_image, dst_row)
+            _native.run("gsr_resize_f32", device, src, src_image, src_row, n, H, W, _native.RESIZE_HORIZONTAL, Wo, bounds,
+                        table, ksize, dst, dst_image, dst_row)
         else:
-            _native.run("gsr_resize_u8", device, _native.ptr(src), src_image, src_row, n, H, W, C, _native.RESIZE_HORIZONTAL, Wo, _native.ptr(bounds),
-                        _native.ptr(table), ksize, _native.ptr(dst), dst_image, dst_row, ep)
+            _native.run("gsr_resize_u8", device, src, src_image, src_row, n, H, W, C, _native.RESIZE_HORIZONTAL, Wo, bounds,
+                        table, ksize, dst, dst_image, dst_row, ep)
         launches += 1
         src, src_image, src_row, cur_W = dst, dst_image, dst_row, Wo
     if H != Ho:
         bounds, table, ksize = _device_tables(device, kind, H, Ho, resample)
         if f32:
-            _native.run("gsr_resize_f32", device, _native.ptr(src), src_image, src_row, n, H, cur_W, _native.RESIZE_VERTICAL, Ho, _native.ptr(bounds),
-                        _native.ptr(table), ksize, _native.ptr(out4), out_image, out_row)
+            _native.run("gsr_resize_f32", device, src, src_image, src_row, n, H, cur_W, _native.RESIZE_VERTICAL, Ho, bounds,
+                        table, ksize, out4, out_image, out_row)
         else:
-            _native.run("gsr_resize_u8", device, _native.ptr(src), src_image, src_row, n, H, cur_W, C, _native.RESIZE_VERTICAL, Ho, _native.ptr(bounds),
-                        _native.ptr(table), ksize, _native.ptr(out4), out_image, out_row, epilogue)
+            _native.run("gsr_resize_u8", device, src, src_image, src_row, n, H, cur_W, C, _native.RESIZE_VERTICAL, Ho, bounds,
+                        table, ksize, out4, out_image, out_row, epilogue)
         launches += 1
     return launches
 

@@ -148,14 +148,7 @@ def hip_run(s, grads=None, device="cuda", debug=False, keep_state=False, rs=None
     if rg and not keep_state and color.grad_fn is not None and s["means3D"].shape[0] > 0:
         # where every pixel's walk ended (decoded from the workspaces autograd holds, before the backward consumes anything): the
         # Gaussian blended last and the final transmittance -- a T = 1e-4 stop that differs from the oracle's shows here directly
-        from gscream_amd import _layout
-        geom, binning, img = color.grad_fn.saved_tensors[-3:]
-        R = int(color.grad_fn.num_rendered)
-        iv = _layout.image_views(img, s["means3D"].shape[0], s["W"], s["H"])
-        bv = _layout.binning_views(binning, R, capacity=int(color.grad_fn.binning_capacity))
-        out["final_T"] = iv["final_T"].cpu().numpy().copy()
-        out["last_gid"] = last_gaussian(iv["ranges"].cpu().numpy().astype(np.int64), bv["point_list"].cpu().numpy().astype(np.int64),
-                                        (iv["n_contrib"].cpu().numpy().astype(np.int64) & 0x3fffffff), s["W"], s["H"])
+        out["final_T"], out["last_gid"] = walk_ends(color, s["means3D"].shape[0], s["W"], s["H"])
     if rg and not keep_state:
         gc, gd, gu = (torch.from_numpy(g).to(device) for g in grads)
         loss = (color * gc).sum() + (depth * gd).sum() + (unc * gu).sum()
@@ -174,6 +167,20 @@ def hip_run(s, grads=None, device="cuda", debug=False, keep_state=False, rs=None
         if "cov3D_precomp" in kw:
             out["dL_dcov3D"] = kw["cov3D_precomp"].grad.cpu().numpy()
     return out
+
+
+def walk_ends(color, P, W, H):
+    """(final_T [H, W], last_gid [H, W]) of the forward that produced the rendered image `color` (a tensor still attached to its
+    rasterizer node, from GaussianRasterizer or from gaussian_renderer.render), decoded from the workspaces autograd holds for the
+    backward.  P: the number of Gaussians that forward was given."""
+    from gscream_amd import _layout
+    geom, binning, img = color.grad_fn.saved_tensors[-3:]
+    R = int(color.grad_fn.num_rendered)
+    iv = _layout.image_views(img, P, W, H)
+    bv = _layout.binning_views(binning, R, capacity=int(color.grad_fn.binning_capacity))
+    last = last_gaussian(iv["ranges"].cpu().numpy().astype(np.int64), bv["point_list"].cpu().numpy().astype(np.int64),
+                         (iv["n_contrib"].cpu().numpy().astype(np.int64) & 0x3fffffff), W, H)
+    return iv["final_T"].cpu().numpy().copy(), last
 
 
 def last_gaussian(ranges, point_list, n_contrib, W, H):

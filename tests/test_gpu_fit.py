@@ -1,6 +1,10 @@
 """End to end under a real optimiser: train.py's iteration (prefilter -> decode -> rasterize -> RGB + depth losses -> backward ->
 training_statis -> Adam step with the reference's parameter groups, gscream_amd/fit.py) against images of a synthetic teacher scene.
 If any gradient of the chain pointed the wrong way, or the rows disagreed about layouts, the loss would not fall.
+Not checked here: anything smaller than a wrong direction.  The loss still falls with opacity and uncertainty gradients swapped
+between the rasterizer and the decode, with the depth gradient dropped or mis-scaled, with viewspace_points.grad in other units, with
+non-zero gradient rows on hidden anchors, or with stale decode bookkeeping; tests/test_gpu_iteration.py audits those seams one by
+one against the chained oracles.
 Reference: train.py:414-416, 433, 527, 535-575, 597-602, 627; scene/gaussian_model.py:350-395; arguments/__init__.py:93-133."""
 import os
 import sys

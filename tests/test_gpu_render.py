@@ -1,5 +1,10 @@
 """End-to-end: gscream_amd.gaussian_renderer.render / prefilter_voxel (decode -> rasterize on the HIP rows) against the
-CPU oracles chained the same way (oracle decode in float64 -> C oracle rasterizer)."""
+CPU oracles chained the same way (oracle decode in float64 -> C oracle rasterizer).
+
+Not checked here: the gradients.  The test below compares the forward images; of the backward it asserts only that every
+parameter's gradient exists, is finite and is not all zero, so a gradient routed to the wrong input, scaled wrongly or left in
+hidden rows passes.  tests/test_gpu_iteration.py holds every gradient that crosses a module boundary, and every final parameter
+gradient, against the chained oracles."""
 import math
 import os
 import sys

@@ -157,6 +157,8 @@ def _stub_the_launches(monkeypatch):
     from gscream_amd import _native
     stub = _Stub()
     monkeypatch.setattr(_native, "run", lambda name, device, *args: getattr(stub, name)(*args))
+    # (the pointers go to the stub, never to a kernel: ptr() without its refusal of host memory)
+    monkeypatch.setattr(_native, "ptr", lambda t: None if t is None or t.numel() == 0 else _native.ctypes.c_void_p(t.data_ptr()))
     monkeypatch.setattr(Z, "_on_device", lambda x, resample: not Z.force_host and resample != Z.HAMMING and x.dtype in (torch.uint8, torch.float32))
     real_to = torch.Tensor.to
     monkeypatch.setattr(torch.Tensor, "to", lambda self, *a, **k: self if a and isinstance(a[0], torch.device) and a[0].type == "cuda" else real_to(self, *a, **k))
