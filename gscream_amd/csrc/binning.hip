@@ -13,6 +13,7 @@
 // HBM traffic: hist reads rect + mask (16 B/G); table NB*T*4 B written, scanned, read; scatter reads 24 B/G and
 // writes 4 B/instance (the id) + 16 B/G (record tail); sort reads 4 B + a 4-B depth gather and writes 4 B per instance.
 #include "gsr_math.h"
+#include "gsr_reduce.h"
 #include "gsr_scan.h"
 
 typedef unsigned long long u64;
@@ -596,22 +597,13 @@ __device__ __forceinline__ void gsr_sort_lds_fused(u64* k, const uint32_t n, con
     }
 }
 
-// Block-wide minimum and maximum of the threads' (mn, mx), in place; red[2 NT / 64].  Holds one barrier.
+// Block-wide minimum and maximum of the threads' (mn, mx), in place, in every thread.  Holds one barrier (gsr_reduce.h).
 template <int NT>
-__device__ __forceinline__ void gsr_block_minmax(u64& mn, u64& mx, u64* red)
+__device__ __forceinline__ void gsr_block_minmax(u64& mn, u64& mx)
 {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        mn = min(mn, (u64)__shfl_xor((unsigned long long)mn, d, 64));
-        mx = max(mx, (u64)__shfl_xor((unsigned long long)mx, d, 64));
-    }
-    if (lane == 0) { red[wave] = mn; red[NW + wave] = mx; }
-    __syncthreads();
-    mn = red[0]; mx = red[NW];
-#pragma unroll
-    for (int w = 1; w < NW; w++) { mn = min(mn, red[w]); mx = max(mx, red[NW + w]); }
+    u64 v[2] = { mn, mx };
+    gsr_block_reduce_all<NT>(v, [](int q, u64 a, u64 b) { return q == 0 ? min(a, b) : max(a, b); });
+    mn = v[0]; mx = v[1];
 }
 
 // Counting sort of one tile list held in registers (n <= NT * KPT keys, thread t owns keys t, t + NT, ...), two levels, O(n)
@@ -633,7 +625,7 @@ __device__ __forceinline__ void gsr_block_minmax(u64& mn, u64& mx, u64* red)
 // NT threads, KPT keys per thread in registers (n <= NT * KPT), 4 * NT buckets (thread t owns buckets 4t .. 4t+3).
 template <int NT, int KPT>
 __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint32_t n, u64* k, uint32_t* offs /*[4 NT]*/,
-                                                 u64* red /*[2 NT / 64]*/, uint32_t* wtot /*[1]: the sum of the squared sub-bucket counts*/)
+                                                 uint32_t* wtot /*[1]: the sum of the squared sub-bucket counts*/)
 {
     constexpr int NB = 4 * NT, LOGNB = NT == 256 ? 10 : 12;
     static_assert(NT == 256 || NT == 1024, "bucket count = 4 NT must match LOGNB");
@@ -644,7 +636,7 @@ __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint
         if ((uint32_t)(t + NT * j) < n) { kmin = min(kmin, v[j]); kmax = max(kmax, v[j]); }
     for (int i = t; i < NB; i += NT) offs[i] = 0u;
     if (t == 0) wtot[0] = 0u;
-    gsr_block_minmax<NT>(kmin, kmax, red);
+    gsr_block_minmax<NT>(kmin, kmax);
     const u64 span = kmax - kmin;
     const int shift = span < (u64)NB ? 0 : (64 - __builtin_clzll(span)) - LOGNB;  // (key - kmin) >> shift < NB
     uint32_t b[KPT];
@@ -736,10 +728,10 @@ __device__ __forceinline__ bool gsr_sort_buckets(const u64 (&v)[KPT], const uint
 // One list from registers to its sorted ids at dst[0..n): the bucket sort, the fused network when its keys are clustered.
 // (in_regs = false: the list is longer than NT * KPT and already lies at keys[GSR_PAD(i)], for the network)
 template <int NT, int KPT>
-__device__ __forceinline__ void gsr_sort_list(const u64 (&v)[KPT], const uint32_t n, u64* keys, uint32_t* offs, u64* red, uint32_t* wtot,
+__device__ __forceinline__ void gsr_sort_list(const u64 (&v)[KPT], const uint32_t n, u64* keys, uint32_t* offs, uint32_t* wtot,
                                               uint32_t* __restrict__ dst, const bool in_regs = true)
 {
-    if (in_regs && gsr_sort_buckets<NT, KPT>(v, n, keys, offs, red, wtot)) {  // n, in_regs are block-uniform
+    if (in_regs && gsr_sort_buckets<NT, KPT>(v, n, keys, offs, wtot)) {  // n, in_regs are block-uniform
         for (uint32_t i = threadIdx.x; i < n; i += NT) dst[i] = (uint32_t)keys[i];
     } else {
         if (n > 1) gsr_sort_lds_fused(keys, n, NT);
@@ -761,7 +753,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
     constexpr int KPT = NT == 256 ? 8 : 16;
     extern __shared__ __attribute__((aligned(16))) u64 keys[];
     __shared__ uint32_t offs[4 * NT];
-    __shared__ u64 red[2 * NT / 64];
     __shared__ uint32_t wtot[1];
     if (only_flagged && !only_flagged[blockIdx.x]) return;  // fix-up pass: only the tiles whose sorted prefix ran out
     const uint2 rg = ranges[blockIdx.x];
@@ -784,7 +775,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
         for (uint32_t i = threadIdx.x; i < n; i += NT) keys[GSR_PAD(i)] = seg_keys[rg.x + i];
         __syncthreads();
     }
-    gsr_sort_list<NT, KPT>(v, n, keys, offs, red, wtot, point_list + rg.x, in_regs);  // (!in_regs: v is not read, the network takes keys[])
+    gsr_sort_list<NT, KPT>(v, n, keys, offs, wtot, point_list + rg.x, in_regs);  // (!in_regs: v is not read, the network takes keys[])
     if (sorted_len && threadIdx.x == 0) sorted_len[blockIdx.x] = n;
 }
 
@@ -804,7 +795,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
 {
     __shared__ __attribute__((aligned(16))) u64 keys[GSR_PAD(GSR_NEAR_CAP) + 1];
     __shared__ uint32_t hist[1024];
-    __shared__ u64 red[8];
     __shared__ uint32_t s_pick, s_near, s_far, wtot[1];
     const uint2 rg = ranges[blockIdx.x];
     const uint32_t n = rg.y - rg.x;
@@ -819,7 +809,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
         u64 v[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) v[j] = (uint32_t)(t + 256 * j) < n ? src[t + 256 * j] : 0ull;
-        gsr_sort_list<256, 8>(v, n, keys, hist, red, wtot, point_list + rg.x);
+        gsr_sort_list<256, 8>(v, n, keys, hist, wtot, point_list + rg.x);
         return;  // sorted_len[tile] = n already (tile scan)
     }
     // pass A: key range
@@ -827,7 +817,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
     for (uint32_t i = t; i < n; i += 256) { const u64 k = src[i]; kmin = min(kmin, k); kmax = max(kmax, k); }
     for (int i = t; i < 1024; i += 256) hist[i] = 0u;
     if (t == 0) { s_pick = 0u; s_near = 0u; s_far = 0u; }
-    gsr_block_minmax<256>(kmin, kmax, red);
+    gsr_block_minmax<256>(kmin, kmax);
     const u64 span = kmax - kmin;
     const int shift = span < 1024ull ? 0 : (64 - __builtin_clzll(span)) - 10;  // (k - kmin) >> shift < 1024
     // pass B: histogram of the key buckets
@@ -862,7 +852,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) g
 #pragma unroll
         for (int j = 0; j < 8; j++) v[j] = (uint32_t)(t + 256 * j) < m ? keys[GSR_PAD(t + 256 * j)] : 0ull;
         __syncthreads();
-        gsr_sort_list<256, 8>(v, m, keys, hist, red, wtot, point_list + rg.x);  // m is block-uniform
+        gsr_sort_list<256, 8>(v, m, keys, hist, wtot, point_list + rg.x);  // m is block-uniform
     }
     if (t == 0) sorted_len[blockIdx.x] = m;
 }

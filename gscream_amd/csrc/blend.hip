@@ -41,6 +41,7 @@
 //     the forward and uniform depth-segment tasks, several per wavefront slot, in the backward.
 #include <stdlib.h>
 #include <algorithm>
+#include "gsr_reduce.h"  // gsr_wave_max
 #include "gsr_scan.h"
 
 // Fast-math knobs of the blend inner loops.  Default: exp via v_exp_f32 (the staged conic is the quadratic form

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #define GDL_THREADS 256
 #define GDL_SCALES 4
@@ -30,29 +31,12 @@ struct GdlParams {  // device-resident scalars shared by the passes
     float loss, l1_mean, smooth, pad2;
 };
 
-// Workgroup sums of NV values with ONE barrier: lanes by xor-shuffle, then the four waves in order; the totals end up in tot[NV]
-// (LDS), valid for every thread after the call.  (The first version reduced one value at a time, two barriers each: the sums kernel
-// spent its time in 18 barriers, the one-block finishers in 9 dependent rounds of strided loads.)
+// Totals of the per-workgroup partials part[nparts][NV] (one block), in every thread: a thread takes whole rows (NV independent loads
+// each, rows t, t + 256, ... in order), then one workgroup sum with one barrier.  (The first version reduced one value at a time, two
+// barriers each: the sums kernel spent its time in 18 barriers, the one-block finishers in 9 dependent rounds of strided loads.)
 template <int NV>
-__device__ __forceinline__ void gdl_block_sums(double (&v)[NV], double* red /*[NV * 4]*/, double* tot /*[NV]*/)
+__device__ __forceinline__ void gdl_total_partials(int nparts, const double* __restrict__ part, double (&v)[NV])
 {
-#pragma unroll
-    for (int i = 0; i < NV; i++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v[i] += __shfl_xor(v[i], d, 64);
-        if ((threadIdx.x & 63) == 0) red[i * 4 + (threadIdx.x >> 6)] = v[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) tot[threadIdx.x] = ((red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + red[threadIdx.x * 4 + 2]) + red[threadIdx.x * 4 + 3];
-    __syncthreads();
-}
-
-// Totals of the per-workgroup partials part[nparts][NV] (one block): every thread takes whole rows (NV independent loads each,
-// rows t, t + 256, ... in order), then one workgroup sum.
-template <int NV>
-__device__ __forceinline__ void gdl_total_partials(int nparts, const double* __restrict__ part, double* red, double* tot)
-{
-    double v[NV];
 #pragma unroll
     for (int i = 0; i < NV; i++) v[i] = 0.0;
     for (int b = threadIdx.x; b < nparts; b += GDL_THREADS) {
@@ -62,7 +46,7 @@ __device__ __forceinline__ void gdl_total_partials(int nparts, const double* __r
 #pragma unroll
         for (int i = 0; i < NV; i++) v[i] += r[i];
     }
-    gdl_block_sums<NV>(v, red, tot);
+    gsr_block_reduce_all<GDL_THREADS>(v, gsr_add());
 }
 
 // pass 1: normal-equation sums over the fit mask, and the gradient-mask sums of the four lattices
@@ -71,7 +55,6 @@ __global__ void __launch_bounds__(GDL_THREADS) gdl_sums_kernel(int H, int W, con
                                                                const float* __restrict__ lsq_mask,
                                                                const float* __restrict__ grad_mask, double* __restrict__ part)
 {
-    __shared__ double red[(5 + GDL_SCALES) * 4], tot[5 + GDL_SCALES];
     double acc[5 + GDL_SCALES] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     const int N = H * W;
     for (int p = blockIdx.x * GDL_THREADS + threadIdx.x; p < N; p += gridDim.x * GDL_THREADS) {
@@ -84,8 +67,10 @@ __global__ void __launch_bounds__(GDL_THREADS) gdl_sums_kernel(int H, int W, con
         for (int k = 0; k < GDL_SCALES; k++)
             if (((x | yy) & ((1 << k) - 1)) == 0) acc[5 + k] += (double)g;
     }
-    gdl_block_sums<5 + GDL_SCALES>(acc, red, tot);
-    if (threadIdx.x < 5 + GDL_SCALES) part[(size_t)blockIdx.x * (5 + GDL_SCALES) + threadIdx.x] = tot[threadIdx.x];
+    gsr_block_reduce<GDL_THREADS>(acc, gsr_add());
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int i = 0; i < 5 + GDL_SCALES; i++) part[(size_t)blockIdx.x * (5 + GDL_SCALES) + i] = acc[i];
 }
 
 // the least-squares fit and the constants of the passes from the totals of pass 1 (one thread)
@@ -119,22 +104,18 @@ __global__ void __launch_bounds__(GDL_THREADS) gdl_stencil_kernel(int H, int W, 
                                                                   float lambda_smooth, GdlParams* __restrict__ P, float* __restrict__ G,
                                                                   double* __restrict__ part)
 {
-    __shared__ double red[(5 + GDL_SCALES) * 4], tot[5 + GDL_SCALES];
-    __shared__ GdlParams sq;
     // The fit is folded in: EVERY workgroup totals the partials of pass 1 (nparts1 x 9 doubles, L2 hits; the same fixed order
     // everywhere, so all of them get the same bits) and solves the 2 x 2 system -- a launch of its own for that cost 4.6 us between two
-    // kernels of 6 and 17.  Workgroup 0 leaves the parameters for the finisher and the backward.
-    gdl_total_partials<5 + GDL_SCALES>(nparts1, part1, red, tot);
-    if (threadIdx.x == 0) {
-        sq = gdl_fit(tot, H, W, lambda_l1, lambda_smooth);
-        if (blockIdx.x == 0) *P = sq;
-    }
-    __syncthreads();
+    // kernels of 6 and 17.  The totals are valid in every thread, so every thread solves it (the same bits again): no LDS copy of
+    // the parameters, no barrier for it.  Workgroup 0 leaves the parameters for the finisher and the backward.
+    double tot[5 + GDL_SCALES];
+    gdl_total_partials(nparts1, part1, tot);
+    const GdlParams sq = gdl_fit(tot, H, W, lambda_l1, lambda_smooth);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *P = sq;
     const float s = sq.s, t = sq.shift, cl1 = sq.cl1;
     float cs[GDL_SCALES];
 #pragma unroll
     for (int k = 0; k < GDL_SCALES; k++) cs[k] = sq.cs[k];
-    __syncthreads();  // (red / tot are used again for this pass's own sums)
     double acc[3 + GDL_SCALES] = { 0, 0, 0, 0, 0, 0, 0 };  // l1 sum, sum G, sum G d, edge sums per scale
     auto diff = [&](int x, int y) {  // g (a - y) at a pixel (gradient_loss :62-63)
         const int q = y * W + x;
@@ -180,15 +161,17 @@ __global__ void __launch_bounds__(GDL_THREADS) gdl_stencil_kernel(int H, int W, 
         acc[1] += (double)g;
         acc[2] += (double)g * (double)d;
     }
-    gdl_block_sums<3 + GDL_SCALES>(acc, red, tot);
-    if (threadIdx.x < 3 + GDL_SCALES) part[(size_t)blockIdx.x * (3 + GDL_SCALES) + threadIdx.x] = tot[threadIdx.x];
+    gsr_block_reduce<GDL_THREADS>(acc, gsr_add());
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int i = 0; i < 3 + GDL_SCALES; i++) part[(size_t)blockIdx.x * (3 + GDL_SCALES) + i] = acc[i];
 }
 
 __global__ void __launch_bounds__(GDL_THREADS) gdl_finish_kernel(int nparts, int H, int W, const double* __restrict__ part,
                                                                  float lambda_l1, GdlParams* __restrict__ P, float* __restrict__ out)
 {
-    __shared__ double red[(3 + GDL_SCALES) * 4], tot[3 + GDL_SCALES];
-    gdl_total_partials<3 + GDL_SCALES>(nparts, part, red, tot);
+    double tot[3 + GDL_SCALES];
+    gdl_total_partials(nparts, part, tot);
     if (threadIdx.x == 0) {
         GdlParams q = *P;
         const double l1_mean = tot[0] / ((double)H * (double)W);

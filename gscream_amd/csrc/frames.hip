@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -39,33 +40,14 @@ static_assert(sizeof(FrmTable) <= 1024, "the table travels in the kernel argumen
 
 // ---- stats ----
 // slots 0 .. 4 and 7 add, 5 takes the minimum, 6 the maximum (never NaN: the comparisons that fill them reject it)
-__device__ __forceinline__ double frm_join(int q, double a, double b)
-{
-    if (q == 5) return b < a ? b : a;
-    if (q == 6) return b > a ? b : a;
-    return a + b;
-}
-
-// over the wave by xor-butterfly (a fixed tree), then over the waves in order; the result is valid in thread 0
-__device__ __forceinline__ void frm_block_join8(double (&v)[8], double* red /* [FRM_THREADS/64][8] */)
-{
-#pragma unroll
-    for (int q = 0; q < 8; q++)
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v[q] = frm_join(q, v[q], __shfl_xor(v[q], s, 64));
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < 8; q++) red[wave * 8 + q] = v[q];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            double s = red[q];
-            for (int w = 1; w < FRM_THREADS / 64; w++) s = frm_join(q, s, red[w * 8 + q]);
-            v[q] = s;
-        }
-}
+struct frm_join {
+    __device__ __forceinline__ double operator()(int q, double a, double b) const
+    {
+        if (q == 5) return b < a ? b : a;
+        if (q == 6) return b > a ? b : a;
+        return a + b;
+    }
+};
 
 __device__ __forceinline__ void frm_extrema(float x, double (&acc)[8])
 {
@@ -83,7 +65,6 @@ __global__ void __launch_bounds__(FRM_THREADS) frame_stats_partial_kernel(int HW
                                                                           const float* __restrict__ mask, const float* __restrict__ params,
                                                                           double* __restrict__ partials)
 {
-    __shared__ double red[(FRM_THREADS / 64) * 8];
     const int b = (int)blockIdx.y;
     const size_t base = (size_t)b * (size_t)HW;
     const int start = (int)blockIdx.x * FRAME_STATS_CHUNK;  // < HW < 2^29
@@ -115,7 +96,7 @@ __global__ void __launch_bounds__(FRM_THREADS) frame_stats_partial_kernel(int HW
             frm_extrema(target[base + (size_t)i], acc);
         }
     }
-    frm_block_join8(acc, red);
+    gsr_block_reduce<FRM_THREADS>(acc, frm_join());
     if (threadIdx.x == 0) {
         double* out = partials + ((size_t)b * (size_t)gridDim.x + (size_t)blockIdx.x) * 8;
 #pragma unroll
@@ -127,14 +108,13 @@ template <int PASS>
 __global__ void __launch_bounds__(FRM_THREADS) frame_stats_finish_kernel(int chunks, const double* __restrict__ partials, double* __restrict__ stats,
                                                                          float* __restrict__ params)
 {
-    __shared__ double red[(FRM_THREADS / 64) * 8];
     const int b = (int)blockIdx.x;
     const double* in = partials + (size_t)b * (size_t)chunks * 8;
     double acc[8] = FRM_ACC_INIT;
     for (int i = threadIdx.x; i < chunks; i += FRM_THREADS)
 #pragma unroll
-        for (int q = 0; q < 8; q++) acc[q] = frm_join(q, acc[q], in[(size_t)i * 8 + q]);
-    frm_block_join8(acc, red);
+        for (int q = 0; q < 8; q++) acc[q] = frm_join()(q, acc[q], in[(size_t)i * 8 + q]);
+    gsr_block_reduce<FRM_THREADS>(acc, frm_join());
     if (threadIdx.x != 0) return;
     const float nan = __builtin_nanf("");
     const float lo = acc[7] > 0.0 ? nan : (float)acc[5], hi = acc[7] > 0.0 ? nan : (float)acc[6];  // (fp32 values: the casts are exact)

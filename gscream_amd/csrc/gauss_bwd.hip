@@ -12,6 +12,7 @@
 //
 // HBM traffic per Gaussian: read 48 B x traversed instances (the slots the backward blend actually wrote) + inputs;
 // write 12 + 12 + 4 + 4 + 12 + 12 + 16 = 72 B.
+#include "gsr_reduce.h"  // gsr_wave_max
 #include "gsr_scan.h"  // (and gsr_math.h through it)
 
 // DGR backward.cu:20-139 computeColorFromSH (bwd): returns dL/dmean contribution, writes dL/dsh.

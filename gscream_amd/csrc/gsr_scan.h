@@ -1,7 +1,8 @@
 // gsr_scan.h -- the scans and the ordered compaction ("count, scan, place") of the kernels around the rasterizer: decode,
 // kNN, anchor growth, anchor sampling -- and of the rasterizer's binning (binning.hip: gsr_block_scan_runs and the C = 4 form) and per-Gaussian
-// backward (gauss_bwd.hip: the written-slot counts of a flag pass across the cooperative kernel's four waves, gsr_wave_max).
-// Integer sums only, with one fixed association order per output element.  (gsr_fwd_order_block keeps its own scan.)
+// backward (gauss_bwd.hip: the written-slot counts of a flag pass across the cooperative kernel's four waves).
+// Integer sums only, with one fixed association order per output element.  (gsr_fwd_order_block keeps its own scan; the reductions
+// are in gsr_reduce.h.)
 //
 // The block-wide forms keep their per-wave totals in a static LDS array and hold exactly ONE barrier: a kernel that calls
 // the same form a second time needs a __syncthreads() between the two calls (binning.hip does, and has one).  All threads
@@ -18,15 +19,6 @@ __device__ __forceinline__ unsigned long long gsr_wave_scan_add(unsigned long lo
         const unsigned long long t = __shfl_up(v, d, 64);
         if (lane >= d) v += t;
     }
-    return v;
-}
-
-// maximum over the wave, in every lane (int or uint32_t)
-template <typename T>
-__device__ __forceinline__ T gsr_wave_max(T v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (T)__shfl_xor((int)v, d, 64));
     return v;
 }
 

@@ -26,6 +26,7 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "gsr_reduce.h"
 #include "gsr_scan.h"
 
 #define GSK_BOX 64
@@ -33,28 +34,24 @@
 
 struct GskBox { float lo[3], hi[3]; };
 
+// the join of a box and what rides along with it: slots 0 .. 2 take the minimum, the slots behind them the maximum
+struct gsk_lo3_hi {
+    __device__ __forceinline__ float operator()(int k, float a, float b) const { return k < 3 ? fminf(a, b) : fmaxf(a, b); }
+};
+
 // ---- bounding box of the cloud (simple_knn.cu:190-199; the reference's reduction starts from {0,0,0}, which only
 // moves the Morton grid, never the result -- kept for identical ordering of equal codes) ----
 __global__ void __launch_bounds__(256) gsk_minmax_kernel(int P, const float* __restrict__ pts, float* __restrict__ part)
 {
-    __shared__ float red[6][256];
-    float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 0.f, 0.f, 0.f };
+    float v[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };  // lo[3], hi[3]
     for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256)
 #pragma unroll
-        for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)i + k]; lo[k] = fminf(lo[k], v); hi[k] = fmaxf(hi[k], v); }
+        for (int k = 0; k < 3; k++) { const float x = pts[3 * (size_t)i + k]; v[k] = fminf(v[k], x); v[3 + k] = fmaxf(v[3 + k], x); }
+    // (fminf / fmaxf drop a NaN and the seed is a number, so no NaN gets through and the result does not depend on the order of the joins)
+    gsr_block_reduce<256>(v, gsk_lo3_hi());
+    if (threadIdx.x == 0)
 #pragma unroll
-    for (int k = 0; k < 3; k++) { red[k][threadIdx.x] = lo[k]; red[3 + k][threadIdx.x] = hi[k]; }
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s)
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                red[k][threadIdx.x] = fminf(red[k][threadIdx.x], red[k][threadIdx.x + s]);
-                red[3 + k][threadIdx.x] = fmaxf(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
+        for (int k = 0; k < 6; k++) part[blockIdx.x * 6 + k] = v[k];
 }
 
 __device__ __forceinline__ uint32_t gsk_prep_morton(uint32_t x)  // simple_knn.cu:40-47
@@ -136,10 +133,8 @@ __global__ void __launch_bounds__(GSK_BOX) gsk_box_kernel(int P, const float4* _
         const float4 p = sp[i];
         lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], d, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d, 64)); }
+    gsr_wave_reduce(lo, gsr_min());
+    gsr_wave_reduce(hi, gsr_max());
     if (threadIdx.x == 0) {
         GskBox b;
 #pragma unroll
@@ -158,10 +153,8 @@ __global__ void __launch_bounds__(GSK_BOX) gsk_superbox_kernel(int nboxes, const
 #pragma unroll
         for (int k = 0; k < 3; k++) { lo[k] = b.lo[k]; hi[k] = b.hi[k]; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], d, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d, 64)); }
+    gsr_wave_reduce(lo, gsr_min());
+    gsr_wave_reduce(hi, gsr_max());
     if (threadIdx.x == 0) {
         GskBox b;
 #pragma unroll
@@ -203,8 +196,6 @@ __global__ void __launch_bounds__(GSK_GROUP) gsk_search_kernel(int P, int nboxes
                                                                float* __restrict__ mean_dist2)
 {
     __shared__ float4 cand[GSK_BOX];
-    __shared__ float red[7][GSK_GROUP / 64];
-    __shared__ float grp[7];  // group bounding box lo[3], hi[3], largest reject
     const int t = threadIdx.x, i = blockIdx.x * GSK_GROUP + t;
     const bool live = i < P;
     const float4 me = live ? sp[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -216,28 +207,12 @@ __global__ void __launch_bounds__(GSK_GROUP) gsk_search_kernel(int P, int nboxes
     const float reject = best[2];
     best[0] = best[1] = best[2] = FLT_MAX;
 
-    // group bounding box and largest reject radius
+    // group bounding box lo[3], hi[3] and largest reject radius, in every thread
     float v[7] = { live ? me.x : FLT_MAX, live ? me.y : FLT_MAX, live ? me.z : FLT_MAX,
                    live ? me.x : -FLT_MAX, live ? me.y : -FLT_MAX, live ? me.z : -FLT_MAX, live ? reject : 0.f };
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-            const float o = __shfl_xor(v[k], d, 64);
-            v[k] = k < 3 ? fminf(v[k], o) : fmaxf(v[k], o);
-        }
-    if ((t & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 7; k++) red[k][t >> 6] = v[k];
-    __syncthreads();
-    if (t < 7) {
-        float r = red[t][0];
-        for (int w = 1; w < GSK_GROUP / 64; w++) r = t < 3 ? fminf(r, red[t][w]) : fmaxf(r, red[t][w]);
-        grp[t] = r;
-    }
-    __syncthreads();
-    const float glo[3] = { grp[0], grp[1], grp[2] }, ghi[3] = { grp[3], grp[4], grp[5] };
-    const float greject = grp[6];
+    gsr_block_reduce_all<GSK_GROUP>(v, gsk_lo3_hi());
+    const float glo[3] = { v[0], v[1], v[2] }, ghi[3] = { v[3], v[4], v[5] };
+    const float greject = v[6];
 
     for (int b = 0; b < nboxes; b++) {
         if ((b & (GSK_BOX - 1)) == 0 && gsk_box_box(glo, ghi, sboxes[b / GSK_BOX]) > greject) {  // 64 boxes rejected at once

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #define GSL_TW 32
 #define GSL_TH 16
@@ -53,7 +54,6 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
     const float* GSL_G = taps.g;
     __shared__ float sx[GSL_HH][GSL_HW + 1], sy[GSL_HH][GSL_HW + 1];
     __shared__ float hx[4][GSL_HH][GSL_TW];
-    __shared__ double red[2][4];
     const int t = threadIdx.x, ch = blockIdx.z;
     const int x0 = blockIdx.x * GSL_TW, y0 = blockIdx.y * GSL_TH;
     const size_t plane = (size_t)H * W;
@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
         }
     }
     __syncthreads();
-    double l1sum = 0.0, ssum = 0.0;
+    double sums[2] = { 0.0, 0.0 };  // |x - y| m, ssim m
     // vertical pass: a thread finishes two vertically adjacent pixels from a 12-row register window
     const int vc = t % GSL_TW, vr = (t / GSL_TW) * 2;
     float col[4][12];
@@ -132,8 +132,8 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
             const float ssim = A * B * inv;
             const float m = weight ? weight[(size_t)py * W + px] : 1.0f;
             const float x = sx[r + GSL_R][c + GSL_R], y = sy[r + GSL_R][c + GSL_R];
-            l1sum += (double)(fabsf(x - y) * m);
-            ssum += (double)(ssim * m);
+            sums[0] += (double)(fabsf(x - y) * m);
+            sums[1] += (double)(ssim * m);
             if (STATE) {
                 // partial derivatives of ssim w.r.t. mu1, E[x^2], E[xy] (sigma1^2 = E11 - mu1^2, sigma12 = E12 - mu1 mu2)
                 const float dmu1 = (2.f * mu2 * (B - A) - 2.f * mu1 * ssim * (D - Cc)) * inv;
@@ -144,15 +144,11 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
             }
         }
     }
-    // workgroup sums (fixed order: lanes by xor-shuffle, then the four waves)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { l1sum += __shfl_xor(l1sum, d, 64); ssum += __shfl_xor(ssum, d, 64); }
-    if ((t & 63) == 0) { red[0][t >> 6] = l1sum; red[1][t >> 6] = ssum; }
-    __syncthreads();
+    gsr_block_reduce<256>(sums, gsr_add());  // (the fixed order of gsr_reduce.h)
     if (t == 0) {
         GslPartial p;
-        p.l1 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        p.ssim = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        p.l1 = sums[0];
+        p.ssim = sums[1];
         partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = p;
     }
 }
@@ -161,16 +157,11 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
 __global__ void __launch_bounds__(256) gsl_finish_kernel(int nparts, const GslPartial* __restrict__ partial, double count,
                                                          float a_l1, float a_ssim, float* __restrict__ out)
 {
-    __shared__ double red[2][4];
-    double l1 = 0.0, ss = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) { l1 += partial[i].l1; ss += partial[i].ssim; }
-    // (lanes by xor-shuffle, then the four waves: one barrier instead of the eight of an LDS tree)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { l1 += __shfl_xor(l1, d, 64); ss += __shfl_xor(ss, d, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = l1; red[1][threadIdx.x >> 6] = ss; }
-    __syncthreads();
+    double sums[2] = { 0.0, 0.0 };
+    for (int i = threadIdx.x; i < nparts; i += 256) { sums[0] += partial[i].l1; sums[1] += partial[i].ssim; }
+    gsr_block_reduce<256>(sums, gsr_add());  // (one barrier instead of the eight of an LDS tree)
     if (threadIdx.x == 0) {
-        const double ml1 = (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / count, mss = (((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / count;
+        const double ml1 = sums[0] / count, mss = sums[1] / count;
         out[0] = (float)((double)a_l1 * ml1 + (double)a_ssim * mss);
         out[1] = (float)ml1;
         out[2] = (float)mss;

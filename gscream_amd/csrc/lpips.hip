@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -172,24 +173,10 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_pool_kernel(long long total 
     out[e] = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[W], p[W + 1]));
 }
 
-// sum over the wave by xor-butterfly (a fixed tree), then over the waves in order; valid in thread 0
-__device__ __forceinline__ double lp_block_sum(double v, double* red /* [LP_THREADS / 64] */)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int w = 1; w < LP_THREADS / 64; w++) s += red[w];
-    __syncthreads();  // (red may be used again)
-    return s;
-}
-
 __global__ void __launch_bounds__(LP_THREADS) lpips_head_kernel(int B, int C, long long hw, const float* __restrict__ feat /* [2B,C,hw] */,
                                                                const float* __restrict__ lin, float* __restrict__ map /* [B,hw] */,
                                                                double* __restrict__ partials /* [B,gridDim.x] */)
 {
-    __shared__ double red[LP_THREADS / 64];
     const int b = (int)blockIdx.y;
     const long long p = (long long)blockIdx.x * LP_THREADS + threadIdx.x;
     double m = 0.0;
@@ -210,7 +197,7 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_head_kernel(int B, int C, lo
         }
         map[(size_t)b * (size_t)hw + (size_t)p] = (float)m;
     }
-    const double s = lp_block_sum(m, red);
+    const double s = gsr_block_reduce_all<LP_THREADS>(m, gsr_add());
     if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = s;
 }
 
@@ -236,7 +223,6 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_spatial_kernel(int H, int W,
                                                                   long long mask_stride_b, float* __restrict__ spatial /* [B,H,W] or NULL */,
                                                                   double* __restrict__ partials /* [B,gridDim.x,2] */)
 {
-    __shared__ double red[LP_THREADS / 64];
     const int b = (int)blockIdx.y;
     const long long hw = (long long)H * W, p = (long long)blockIdx.x * LP_THREADS + threadIdx.x;
     double value = 0.0, count = 0.0;
@@ -262,7 +248,9 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_spatial_kernel(int H, int W,
             count = 1.0;
         }
     }
-    const double vs = lp_block_sum(value, red), cs = lp_block_sum(count, red);
+    const double vs = gsr_block_reduce_all<LP_THREADS>(value, gsr_add());
+    __syncthreads();
+    const double cs = gsr_block_reduce_all<LP_THREADS>(count, gsr_add());
     if (threadIdx.x == 0) {
         double* o = partials + ((size_t)b * gridDim.x + blockIdx.x) * 2;
         o[0] = vs;
@@ -281,14 +269,14 @@ struct lp_finish_args {
 __global__ void __launch_bounds__(LP_THREADS) lpips_finish_kernel(lp_finish_args a, float* __restrict__ out_plain, float* __restrict__ out_layers,
                                                                  float* __restrict__ out_masked)
 {
-    __shared__ double red[LP_THREADS / 64];
     const int b = (int)blockIdx.x;
     double total = 0.0;
     for (int l = 0; l < 5; l++) {
         const double* in = a.head[l] + (size_t)b * (size_t)a.blocks[l];
         double v = 0.0;
         for (int i = threadIdx.x; i < a.blocks[l]; i += LP_THREADS) v += in[i];
-        const double mean = lp_block_sum(v, red) / a.pixels[l];
+        const double mean = gsr_block_reduce_all<LP_THREADS>(v, gsr_add()) / a.pixels[l];
+        __syncthreads();  // (before the next sum: gsr_reduce.h)
         if (threadIdx.x == 0 && out_layers) out_layers[(size_t)b * 5 + l] = (float)mean;
         total = l == 0 ? mean : total + mean;
     }
@@ -298,7 +286,9 @@ __global__ void __launch_bounds__(LP_THREADS) lpips_finish_kernel(lp_finish_args
         v += in[2 * (size_t)i];
         c += in[2 * (size_t)i + 1];
     }
-    const double vs = lp_block_sum(v, red), cs = lp_block_sum(c, red);
+    const double vs = gsr_block_reduce_all<LP_THREADS>(v, gsr_add());
+    __syncthreads();
+    const double cs = gsr_block_reduce_all<LP_THREADS>(c, gsr_add());
     if (threadIdx.x == 0) {
         out_plain[b] = (float)total;
         if (out_masked) out_masked[b] = (float)(vs / cs);  // an empty mask: 0/0 = NaN

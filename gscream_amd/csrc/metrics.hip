@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -64,27 +65,6 @@ __device__ __forceinline__ int met_reflect(int g, int n)
     return min(max(g, 0), n - 1);
 }
 
-// sum over the wave by xor-butterfly (a fixed tree), then over the waves in order; the result is valid in thread 0
-__device__ __forceinline__ void met_block_sum8(double (&v)[8], double* red /* [MET_THREADS/64][8] */)
-{
-#pragma unroll
-    for (int q = 0; q < 8; q++)
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v[q] += __shfl_xor(v[q], s, 64);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < 8; q++) red[wave * 8 + q] = v[q];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            double s = red[q];
-            for (int w = 1; w < MET_THREADS / 64; w++) s += red[w * 8 + q];
-            v[q] = s;
-        }
-}
-
 struct met_taps { double g0, g1, g2; };  // g_k = g_{4-k}
 
 __global__ void __launch_bounds__(MET_THREADS) metrics_tile_kernel(int H, int W, int C, int tiles_x, const float* __restrict__ pred,
@@ -94,7 +74,6 @@ __global__ void __launch_bounds__(MET_THREADS) metrics_tile_kernel(int H, int W,
 {
     __shared__ float xs[MET_SH * MET_SW], ys[MET_SH * MET_SW];
     __shared__ double hp[5][MET_SH * MET_TW];
-    __shared__ double red[(MET_THREADS / 64) * 8];
     const int tile = (int)blockIdx.x, plane = (int)blockIdx.y;  // plane = b*C + c
     const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
     const int x0 = tile_x * MET_TW, y0 = tile_y * MET_TH;
@@ -170,7 +149,7 @@ __global__ void __launch_bounds__(MET_THREADS) metrics_tile_kernel(int H, int W,
             acc[7] += ds;
         }
     }
-    met_block_sum8(acc, red);
+    gsr_block_reduce<MET_THREADS>(acc, gsr_add());
     if (threadIdx.x == 0) {
         double* out = partials + ((size_t)plane * (size_t)gridDim.x + (size_t)tile) * 8;
 #pragma unroll
@@ -181,14 +160,13 @@ __global__ void __launch_bounds__(MET_THREADS) metrics_tile_kernel(int H, int W,
 __global__ void __launch_bounds__(MET_THREADS) metrics_finish_kernel(int per_image /* C * tiles */, const double* __restrict__ partials,
                                                                      double* __restrict__ sums, float* __restrict__ metrics)
 {
-    __shared__ double red[(MET_THREADS / 64) * 8];
     const int b = (int)blockIdx.x;
     const double* in = partials + (size_t)b * (size_t)per_image * 8;
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < per_image; i += MET_THREADS)
 #pragma unroll
         for (int q = 0; q < 8; q++) acc[q] += in[(size_t)i * 8 + q];
-    met_block_sum8(acc, red);
+    gsr_block_reduce<MET_THREADS>(acc, gsr_add());
     if (threadIdx.x != 0) return;
 #pragma unroll
     for (int q = 0; q < 8; q++) sums[(size_t)b * 8 + q] = acc[q];

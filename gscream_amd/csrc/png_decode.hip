@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 #include "png_crc.h"
 #include "png_inflate.h"
 
@@ -259,8 +260,7 @@ __global__ void __launch_bounds__(64) png_inflate_kernel(const uint8_t* __restri
 // ---- adler ----
 __global__ void __launch_bounds__(PD_ADLER_THREADS) png_adler_kernel(const gsr_png_file* __restrict__ files, PdWorkspace ws, int32_t* status)
 {
-    __shared__ unsigned long long red[2][PD_ADLER_THREADS / 64];
-    const int f = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = (int)blockIdx.x, tid = (int)threadIdx.x;
     if (status[2 * f] != GSR_PNG_OK) return;  // (written in this kernel only by this workgroup, behind its barrier)
     const gsr_png_file fl = files[f];
     const uint32_t n = (uint32_t)pd_stream_bytes(fl);
@@ -278,19 +278,10 @@ __global__ void __launch_bounds__(PD_ADLER_THREADS) png_adler_kernel(const gsr_p
         const uint32_t i = (n & ~3u) + (uint32_t)tid;
         if (i < n) { A += S[i]; B += (unsigned long long)(n - i) * S[i]; }
     }
-    A %= PNGI_ADLER_MOD;
-    B %= PNGI_ADLER_MOD;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        A += __shfl_xor(A, d, 64);
-        B += __shfl_xor(B, d, 64);
-    }
-    if (lane == 0) { red[0][wave] = A; red[1][wave] = B; }
-    __syncthreads();
+    unsigned long long ab[2] = { A % PNGI_ADLER_MOD, B % PNGI_ADLER_MOD };
+    gsr_block_reduce<PD_ADLER_THREADS>(ab, gsr_add());
     if (tid == 0) {
-        unsigned long long a = 1, b = n;
-        for (int w = 0; w < PD_ADLER_THREADS / 64; w++) { a += red[0][w]; b += red[1][w]; }
-        const uint32_t adler = (uint32_t)(b % PNGI_ADLER_MOD) << 16 | (uint32_t)(a % PNGI_ADLER_MOD);
+        const uint32_t adler = (uint32_t)((n + ab[1]) % PNGI_ADLER_MOD) << 16 | (uint32_t)((1 + ab[0]) % PNGI_ADLER_MOD);
         if (adler != ws.trailer[f]) pd_fail(status, f, GSR_PNG_ADLER);
     }
 }
@@ -368,8 +359,7 @@ __global__ void __launch_bounds__(PD_CRC_THREADS) png_crc_kernel(const uint8_t* 
                                                                  const PngiPiece* __restrict__ pieces, int32_t* status)
 {
     __shared__ uint32_t tab[256];
-    __shared__ uint32_t red[PD_CRC_THREADS / 64];
-    const int p = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = (int)blockIdx.x, tid = (int)threadIdx.x;
     const PngiPiece pc = pieces[p];
     if (pc.file >= (uint32_t)nfiles) return;
     const gsr_png_file fl = files[pc.file];
@@ -384,13 +374,9 @@ __global__ void __launch_bounds__(PD_CRC_THREADS) png_crc_kernel(const uint8_t* 
     for (uint32_t i = lo; i < hi; i++) r = tab[(r ^ src[i]) & 0xffu] ^ (r >> 8);
     uint32_t crc = hi > lo ? png_gf2_mul(r, png_x8n(N - hi)) : 0u;
     if (tid == 0) crc ^= png_gf2_mul(0xffffffffu, png_x8n(N));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d, 64);
-    if (lane == 0) red[wave] = crc;
-    __syncthreads();
+    crc = gsr_block_reduce<PD_CRC_THREADS>(crc, gsr_xor());
     if (tid == 0) {
-        crc = 0xffffffffu;
-        for (int w = 0; w < PD_CRC_THREADS / 64; w++) crc ^= red[w];
+        crc ^= 0xffffffffu;
         const uint8_t* q = src + N;
         const uint32_t stored = (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | (uint32_t)q[3];
         if (crc != stored) pd_fail(status, (int)pc.file, GSR_PNG_CRC);

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "gsr_common.h"
+#include "gsr_reduce.h"
 #include "gsr_scan.h"
 
 #pragma clang fp contract(off)
@@ -316,15 +317,9 @@ __global__ void __launch_bounds__(GSI_THREADS) gsi_vox_range_kernel(int N, const
             for (int a = 0; a < 3; a++) mn[a] = mx[a] = c[a];
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            mn[a] = min(mn[a], __shfl_xor(mn[a], d, 64));
-            mx[a] = max(mx[a], __shfl_xor(mx[a], d, 64));
-        }
-        flags |= (uint32_t)__shfl_xor((int)flags, d, 64);
-    }
+    gsr_wave_reduce(mn, gsr_min());
+    gsr_wave_reduce(mx, gsr_max());
+    flags = gsr_wave_reduce(flags, gsr_or());
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; a++) {
@@ -581,11 +576,7 @@ __global__ void __launch_bounds__(GSI_THREADS) gsi_fill_kernel(int M, int K, int
 #pragma unroll
         for (int a = 0; a < 3; a++) mx[a] = anchors[i * 3 + a];
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, 64));
-    }
+    gsr_wave_reduce(mx, gsr_max());
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; a++) gsi_atomic_max_f32(&xyz_max[a], mx[a]);
