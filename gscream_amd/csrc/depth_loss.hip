@@ -57,12 +57,22 @@ __global__ void __launch_bounds__(GDL_THREADS) gdl_sums_kernel(int H, int W, con
 {
     double acc[5 + GDL_SCALES] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     const int N = H * W;
+    // An absent mask is read through the depth map's pointer (in bounds, a cache hit, the value unused): four unconditional loads in
+    // flight together.  With a branch per mask, each mask's load, its wait and its widening sit inside the branch: two memory round
+    // trips more per pixel, one after the other
+    const float* mp = lsq_mask ? lsq_mask : depth;
+    const float* gp = grad_mask ? grad_mask : depth;
     for (int p = blockIdx.x * GDL_THREADS + threadIdx.x; p < N; p += gridDim.x * GDL_THREADS) {
-        const float d = depth[p], y = target[p], m = lsq_mask ? lsq_mask[p] : 1.0f;
-        acc[0] += (double)(m * d * d); acc[1] += (double)(m * d); acc[2] += (double)m;
-        acc[3] += (double)(m * d * y); acc[4] += (double)(m * y);
+        const float d = depth[p], y = target[p], mv = mp[p], gv = gp[p];
+        const float m = lsq_mask ? mv : 1.0f;
+        // widened BEFORE multiplying: a float32 square carries its own rounding error into a00, and a fit the reference calls
+        // singular (one pixel: d*d * 1 - d * d; pixels of one depth) then has det = that error instead of 0 and solves noise over
+        // noise.  In double the products of a binary mask and two float32 values are exact, so such a det is exactly 0
+        const double md = (double)m * (double)d;
+        acc[0] += md * (double)d; acc[1] += md; acc[2] += (double)m;
+        acc[3] += md * (double)y; acc[4] += (double)m * (double)y;
         const int x = p % W, yy = p / W;
-        const float g = grad_mask ? grad_mask[p] : 1.0f;
+        const float g = grad_mask ? gv : 1.0f;
 #pragma unroll
         for (int k = 0; k < GDL_SCALES; k++)
             if (((x | yy) & ((1 << k) - 1)) == 0) acc[5 + k] += (double)g;
@@ -78,7 +88,9 @@ __device__ __forceinline__ GdlParams gdl_fit(const double* tot /*[5 + GDL_SCALES
 {
     GdlParams q;
     q.a00 = tot[0]; q.a01 = tot[1]; q.a11 = tot[2]; q.b0 = tot[3]; q.b1 = tot[4];
-    q.det = q.a00 * q.a11 - q.a01 * q.a01;                       // loss_utils.py:97
+    // loss_utils.py:97; both products rounded, as the reference's are: contracted into one fma, one of two equal products would be
+    // exact and the other rounded, and a singular fit would again have det = a rounding error
+    q.det = __dsub_rn(__dmul_rn(q.a00, q.a11), __dmul_rn(q.a01, q.a01));
     q.s0 = q.det != 0.0 ? (q.a11 * q.b0 - q.a01 * q.b1) / q.det : 0.0;   // :100
     q.t = q.det != 0.0 ? (-q.a01 * q.b0 + q.a00 * q.b1) / q.det : 0.0;   // :101
     q.s = (float)fabs(q.s0);                                      // train.py:552

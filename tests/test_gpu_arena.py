@@ -305,19 +305,22 @@ def test_rgb_loss(C, H, W, weighted, monkeypatch):
 @pytest.mark.parametrize("H,W", [(1, 33), (9, 17), (64, 64), (142, 252)])
 def test_depth_loss(H, W, monkeypatch):
     """gsr_depth_loss_forward / _backward: one row (no vertical neighbour at any of the four scales), sizes the 2^k subsampling does not
-    divide, a power of two, and the quarter-resolution training frame; without masks, with the three masks, and with the foreground
-    term folded into the weight map."""
+    divide, a power of two, and the quarter-resolution training frame; without masks, with three DISTINCT masks (three buffers of their
+    own between guard bands, so a kernel that reads one in another's place reads other values), and with the foreground term folded
+    into the weight map."""
     from gscream_amd import loss_utils as L
     rng = np.random.default_rng(H * 1000 + W)
     depth = (2.0 + rng.random((1, H, W))).astype(np.float32)
     target = (0.5 * depth + 0.3 + 0.05 * rng.standard_normal(depth.shape)).astype(np.float32)
     mask = (rng.random((1, H, W)) > 0.3).astype(np.float32)
     fg = (rng.random((1, H, W)) > 0.7).astype(np.float32)
+    weight = (1.5 * rng.random((1, H, W)) * (rng.random((1, H, W)) > 0.2)).astype(np.float32)
+    gmask = (rng.random((1, H, W)) > 0.25).astype(np.float32)
 
     def run(arena):
         out = {}
         y, m, f = dev(target), dev(mask), dev(fg)
-        for how, kw in (("plain", {}), ("masked", dict(lsq_mask=m, l1_weight=m, grad_mask=m)), ("fg", dict(lsq_mask=m, fg_mask=f, lambda_fg=99.0))):
+        for how, kw in (("plain", {}), ("masked", dict(lsq_mask=m, l1_weight=dev(weight), grad_mask=dev(gmask))), ("fg", dict(lsq_mask=m, fg_mask=f, lambda_fg=99.0))):
             d = dev(depth).requires_grad_(True)
             loss, parts = L.depth_loss(d, y, lambda_l1=1.0, lambda_smooth=0.5, return_parts=True, **kw)
             (1.3 * loss).backward()
