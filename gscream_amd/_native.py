@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "gsr_lpips_workspace_bytes", "gsr_lpips", "gsr_conv3x3_relu",
     "gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose",
     "gsr_png_capacity", "gsr_png_workspace_bytes", "gsr_png_encode",
+    "gsr_jpeg_capacity", "gsr_jpeg_workspace_bytes", "gsr_jpeg_encode",
     "gsr_png_decode_workspace_bytes", "gsr_png_decode",
     "gsr_sort_block_keys", "gsr_sort_keys_workspace_bytes", "gsr_sort_keys_u64", "gsr_voxelize_workspace_bytes", "gsr_voxelize",
     "gsr_kth_smallest_workspace_bytes", "gsr_kth_smallest_f32", "gsr_scene_init_fill",
@@ -82,6 +83,7 @@ class FramePanel(ctypes.Structure):
 FRAME_MAX_PANELS = 8
 PNG_CHUNK, PNG_HEADER_BYTES, PNG_FILTER_ADAPTIVE = 32768, 16, 5  # GSR_PNG_* of include/gsraster.h
 PNG_PIECE_IDAT, PNG_PIECE_START = 1, 2
+JPEG_HEADER_BYTES, JPEG_INTERVAL_BLOCKS, JPEG_NEED_CAPACITY = 16, 1024, 1  # GSR_JPEG_* of include/gsraster.h
 PNG_STATUS = ("ok", "truncated", "reserved block type", "stored LEN/NLEN mismatch", "over-subscribed or incomplete code", "invalid symbol",
               "distance before the start of the stream", "stream longer than the picture's", "stream shorter than the picture's",
               "filter byte above 4", "Adler-32 mismatch", "CRC-32 mismatch", "table entry out of bounds")  # GSR_PNG_OK .. GSR_PNG_TABLE
@@ -243,6 +245,12 @@ def load():
     lib.gsr_png_workspace_bytes.argtypes = [_c_int] * 4
     lib.gsr_png_encode.restype = _c_int
     lib.gsr_png_encode.argtypes = [_vp, ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 5 + [_vp, ctypes.c_size_t, _vp, _vp]
+    lib.gsr_jpeg_capacity.restype = ctypes.c_size_t
+    lib.gsr_jpeg_capacity.argtypes = [_c_int] * 4
+    lib.gsr_jpeg_workspace_bytes.restype = ctypes.c_size_t
+    lib.gsr_jpeg_workspace_bytes.argtypes = [_c_int] * 6
+    lib.gsr_jpeg_encode.restype = _c_int
+    lib.gsr_jpeg_encode.argtypes = [_vp, ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 7 + [_vp, ctypes.c_size_t, _vp, _vp]
     lib.gsr_png_decode_workspace_bytes.restype = ctypes.c_size_t
     lib.gsr_png_decode_workspace_bytes.argtypes = [ctypes.c_size_t, _c_int, _c_int]
     lib.gsr_png_decode.restype = _c_int

@@ -1319,6 +1319,72 @@ extern "C" int gsr_png_encode(const uint8_t* images, long long row_stride, long 
     return GSR_OK;
 }
 
+// ---- JPEG encoding (jpeg.hip) ----
+static int jpeg_check_sizes(int B, int H, int W, int C, int subsampling)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: B=%d H=%d W=%d (need all > 0)", B, H, W);
+    if (C != 1 && C != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: C=%d (need 1 or 3)", C);
+    if (B > 65535 || H > 65535 || W > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: B=%d H=%d W=%d (need all <= 65535)", B, H, W);
+    if (subsampling != 444 && subsampling != 420) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: subsampling=%d (need 444 or 420)", subsampling);
+    if (subsampling == 420 && C == 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: subsampling 420 with C=1 (a grey picture has no chroma)");
+    if (jpeg_layout(H, W, C, subsampling, 0).capacity >= ((size_t)1 << 31))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: H=%d W=%d C=%d has a capacity of 2^31 bytes or more", H, W, C);
+    return GSR_OK;
+}
+
+static int jpeg_check_interval(int C, int subsampling, int restart_interval)
+{
+    const int most = GSR_JPEG_INTERVAL_BLOCKS / (C == 1 ? 1 : (subsampling == 420 ? 6 : 3));
+    if (restart_interval < 0 || restart_interval > most)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: restart_interval=%d (need 0 = the default, or 1 .. %d MCUs)", restart_interval, most);
+    return GSR_OK;
+}
+
+// a pointer the kernels may use: device memory of this process
+static bool jpeg_on_device(const void* p)
+{
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer: the error is ours to clear)
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice;
+}
+
+extern "C" size_t gsr_jpeg_capacity(int H, int W, int C, int subsampling)
+{
+    return jpeg_check_sizes(1, H, W, C, subsampling) ? 0 : jpeg_layout(H, W, C, subsampling, 0).capacity;
+}
+
+extern "C" size_t gsr_jpeg_workspace_bytes(int B, int H, int W, int C, int subsampling, int restart_interval)
+{
+    if (jpeg_check_sizes(B, H, W, C, subsampling) || jpeg_check_interval(C, subsampling, restart_interval)) return 0;
+    return (size_t)B * jpeg_layout(H, W, C, subsampling, restart_interval).per_picture;
+}
+
+extern "C" int gsr_jpeg_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int quality,
+                               int subsampling, int restart_interval, uint8_t* out, size_t out_stride, void* workspace, void* stream)
+{
+    if (int rc = jpeg_check_sizes(B, H, W, C, subsampling)) return rc;
+    if (int rc = jpeg_check_interval(C, subsampling, restart_interval)) return rc;
+    if (!images || !out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: images, out or workspace is NULL");
+    if (quality < 1 || quality > 100) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: quality=%d (need 1 .. 100)", quality);
+    if (row_stride < (long long)W * C) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: row_stride=%lld is below W*C=%lld", row_stride, (long long)W * C);
+    if (B > 1 && image_stride < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: image_stride=%lld is negative", image_stride);
+    const JpegLayout lay = jpeg_layout(H, W, C, subsampling, restart_interval);
+    const size_t need = GSR_JPEG_HEADER_BYTES + lay.file_header;
+    if (out_stride < need || out_stride % 4 || ((uintptr_t)out & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: out_stride=%zu (need >= %zu = the four words + the file header, a multiple of 4) or out is not 4-byte aligned",
+                        out_stride, need);
+    if ((uintptr_t)workspace & 15) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: workspace is not 16-byte aligned");
+    if (!jpeg_on_device(images) || !jpeg_on_device(out) || !jpeg_on_device(workspace))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: images, out or workspace is not device memory");
+    JpegTables tables;
+    jpeg_fill_tables(&tables, H, W, C, quality, subsampling, lay);
+    GSR_HIP(jpeg_launch_encode(images, row_stride, image_stride, B, H, W, C, tables, lay, out, out_stride, workspace, (hipStream_t)stream), "jpeg encode");
+    return GSR_OK;
+}
+
 // ---- PNG decoding (png_decode.hip) ----
 extern "C" size_t gsr_png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces)
 {

@@ -526,6 +526,29 @@ PngLayout png_layout(int H, int W, int C);
 hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
                              uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream);
 
+// jpeg.hip: uint8 pictures -> baseline JPEG files (validated by the caller).  The workspace holds, per picture, the quantised
+// coefficients (int16 [blocks][64], zigzag order, blocks in scan order), then the intervals' byte counts / file offsets, then one
+// word that says whether the file fits.
+#define JPEG_FILE_HEADER_MAX 640
+struct JpegLayout {
+    int comps, mcu, bpm;                  // components; MCU edge in pixels (8 or 16); blocks per MCU (1, 3, 6)
+    int mcux, mcuy;                       // MCUs per row and per column
+    int ri;                               // MCUs per restart interval (the resolved value)
+    size_t mcus, blocks, intervals;       // per picture
+    size_t file_header;                   // bytes in front of the scan: 629 (C = 3) or 334 (C = 1)
+    size_t sizes_off, fits_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
+    size_t capacity;                      // file_header + 416 blocks + 3 mcus + 2
+};
+struct JpegTables {                       // travels in the kernel arguments
+    uint8_t quant[2][64];                 // natural order, scaled to the quality
+    uint8_t header[JPEG_FILE_HEADER_MAX]; // SOI .. SOS
+};
+JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interval);
+void jpeg_fill_tables(JpegTables* t, int H, int W, int C, int quality, int subsampling, const JpegLayout& lay);
+hipError_t jpeg_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C,
+                              const JpegTables& tables, const JpegLayout& lay, uint8_t* out, size_t out_stride, void* workspace,
+                              hipStream_t stream);
+
 // png_decode.hip: PNG files -> uint8 pictures (pointers and counts validated by the caller; the tables are checked on the device).
 // The workspace holds the files' inflated streams, then per piece {size, flag, offset} of the segment that starts there, then per
 // file the Adler-32 of its trailer.

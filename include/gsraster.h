@@ -714,6 +714,76 @@ int gsr_png_encode(const uint8_t* images, long long row_stride, long long image_
                    uint8_t* out, size_t out_stride, void* workspace, void* stream /* hipStream_t */);
 
 /*
+ * ---- JPEG encoding (jpeg.hip): uint8 pictures -> baseline JPEG files, on the device -------------------------------------------
+ * The lossy frames of the spiral video (gscream_amd/video.py: Motion-JPEG in an AVI), which stands where render_set calls ffmpeg
+ * (train.py:844-846).  A file made here is a baseline sequential JFIF file that any decoder reads; which one it is, byte for byte,
+ * is fixed by these rules (tests/jpeg_helpers.py states them in numpy, gscream_amd/jpeg.py's host path a second time):
+ *
+ *   input      uint8 [H, W, C], C = 1 (grey) or 3 (RGB)
+ *   container  SOI; APP0 "JFIF\0" version 1.01, units 0, density 1:1, no thumbnail; one DQT per table (8-bit, id 0 luminance, id 1
+ *              chrominance, zigzag order); SOF0 (precision 8, H, W, component ids 1, 2, 3, sampling 1x1 1x1 1x1 for 4:4:4 and
+ *              2x2 1x1 1x1 for 4:2:0, quantisation tables 0, 1, 1); DHT DC 0, AC 0, DC 1, AC 1 (grey: DC 0, AC 0; one table per
+ *              segment); DRI; SOS (components with tables 0/0, 1/1, 1/1; Ss 0, Se 63, Ah/Al 0); the scan; EOI; nothing behind EOI.
+ *              A file without restart markers (the host path only) has no DRI segment.
+ *   tables     Huffman: the typical tables of Annex K.3.  Quantisation: Annex K.1 / K.2 scaled as libjpeg does, for quality q = 1 .. 100:
+ *              s = 5000 / q (q < 50, integer division) or 200 - 2 q;  t = clamp((base s + 50) / 100, 1, 255).
+ *   colour     Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *              Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *              Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16          (arithmetic shifts; grey: Y = the input)
+ *   padding    every plane is extended to whole MCUs (8x8; 16x16 for 4:2:0) by repeating its last column, then its last row
+ *   4:2:0      a chroma sample is (a + b + c + d + bias) >> 2 over its 2x2 full-resolution samples, bias 1 in even output columns, 2 in odd
+ *   DCT        C[k][n] = rint(8192 s_k cos((2n + 1) k pi / 16)), s_0 = 1 / sqrt(8), s_k = 1 / 2;  x = sample - 128
+ *              rows:    r[m][k]  = (sum_n C[k][n] x[m][n] + 512) >> 10
+ *              columns: c8[k][j] = (sum_m C[k][m] r[m][j] + 4096) >> 13            (8 x the orthonormal DCT; everything fits int32)
+ *   quantise   v = sign(c8) ((|c8| + 4 Q) / (8 Q)), integer division, Q the table entry of (k, j); coded in zigzag order
+ *   scan       MCUs in raster order; in an MCU the luminance blocks (4:2:0: top left, top right, bottom left, bottom right), Cb, Cr
+ *   entropy    baseline Huffman: the DC difference against the previous block of the same component (0 at the start of an interval)
+ *              as category + value bits; AC as (run, size) symbols + value bits, ZRL for every 16 zeros in front of a non-zero value,
+ *              EOB unless coefficient 63 is non-zero; MSB first; a 0x00 behind every 0xFF byte; an interval's last byte is padded
+ *              with 1 bits
+ *   restart    DRI = Ri MCUs; RSTm (m = 0 .. 7 cycling) between intervals, none behind the last
+ *
+ * An interval holds at most GSR_JPEG_INTERVAL_BLOCKS blocks: Ri <= GSR_JPEG_INTERVAL_BLOCKS / (blocks per MCU: 1 grey, 3 4:4:4, 6 4:2:0).
+ * restart_interval = 0 stands for min(the MCUs of one MCU row, that bound).
+ *
+ * gsr_jpeg_capacity(H, W, C, subsampling): file header + 416 blocks + 3 MCUs + 2, the file header being 629 bytes (C = 3) or 334
+ * (C = 1).  No file of any restart interval is larger: a block is at most 22 + 63 * 26 bits (a DC code of 11 bits and 11 value bits,
+ * 63 AC codes of 16 bits and 10 value bits) = 208 bytes, doubled by stuffing; an interval adds at most a padded byte and a marker,
+ * and a picture has at most as many intervals as MCUs; EOI.  0 for sizes the call rejects.
+ *
+ * gsr_jpeg_encode: images as gsr_png_encode's (byte strides; the inner two dimensions dense, row_stride >= W C, so a panel of a sheet
+ * is read in place).  Picture b's result is out + b*out_stride: GSR_JPEG_HEADER_BYTES of header -- four uint32 words {the file's byte
+ * count, status, restart intervals, 0} -- then the file.  The room for a file is cap = out_stride - GSR_JPEG_HEADER_BYTES, ANY value
+ * from the file header's size up: a file that does not fit has status GSR_JPEG_NEED_CAPACITY, its byte count (what it needs) in
+ * word 0 and nothing written behind the four words; gsr_jpeg_capacity always fits.  Nothing behind a file's last byte is written.
+ * out 4-byte aligned, out_stride a multiple of 4; workspace 16-byte aligned, of gsr_jpeg_workspace_bytes bytes (the coefficients, 128
+ * bytes a block, and 4 bytes per interval), written before it is read.
+ * Four launches on `stream`, no synchronisation, nothing read back, no global atomics, no workgroup waits for another, the same
+ * bytes for the same input:
+ *   transform  a thread per row of an 8x8 block: reads the picture through its strides, converts, pads, downsamples; row pass, LDS,
+ *              column pass, quantise; int16 coefficients in zigzag order, blocks in scan order
+ *   measure    a workgroup per restart interval, a thread per block: token bits, block scan, bits ORed into LDS words in pieces of
+ *              32 KiB, 0xFF bytes counted -> the interval's byte count
+ *   offsets    a workgroup per picture: scan of the interval sizes; the file header (built on the host from the tables compiled
+ *              into the library, carried in the kernel arguments), EOI and the four words
+ *   write      `measure` again, with each piece's bytes stuffed and written straight to their place in the file, and the RST marker
+ * (Measuring and writing in two passes, where gsr_png_encode keeps a slot per chunk, saves a workspace of 416 bytes a block -- three
+ * times the picture -- and a copy; it codes every block twice.)
+ * Rejected before launching (GSR_ERR_INVALID_ARGUMENT): NULL pointers or pointers that are not device memory; B, H or W <= 0; H or
+ * W > 65535; B > 65535; C other than 1, 3; quality outside 1 .. 100; subsampling other than 444, 420 (420 with C = 1); a capacity of
+ * 2^31 or more; row_stride < W C; a negative image_stride; out_stride below header + file header, not a multiple of 4, out or
+ * workspace misaligned; restart_interval < 0 or beyond the bound above.
+ */
+#define GSR_JPEG_HEADER_BYTES 16
+#define GSR_JPEG_INTERVAL_BLOCKS 1024
+#define GSR_JPEG_OK 0
+#define GSR_JPEG_NEED_CAPACITY 1
+size_t gsr_jpeg_capacity(int H, int W, int C, int subsampling);
+size_t gsr_jpeg_workspace_bytes(int B, int H, int W, int C, int subsampling, int restart_interval);
+int gsr_jpeg_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int quality,
+                    int subsampling, int restart_interval, uint8_t* out, size_t out_stride, void* workspace, void* stream /* hipStream_t */);
+
+/*
  * ---- PNG decoding (png_decode.hip, png_inflate.h): the bytes of .png files -> uint8 [H, W, C] pictures, on the device ------------
  * Replaces Image.open + to_tensor + upload in readImages (train.py:887-902) and Scene's picture loading.  The host reads only the
  * chunk headers; inflate, Adler-32, unfilter and CRC-32 run on the device, a batch of files of any sizes in one call.

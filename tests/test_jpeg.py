@@ -1,0 +1,235 @@
+"""The baseline JPEG rules (tests/jpeg_helpers.py) held against PIL -- its decoder reads every file, its encoder is the yardstick for
+size and quality, its files are the source of the tables -- and gscream_amd.jpeg's host path and gscream_amd.video held against the
+helper.  None of this touches the device; tests/test_gpu_jpeg.py holds the device against the same helper.
+
+Margins against PIL's encoder at identical settings, measured with the helper over the corpus below (720 cases) and rounded up to the
+next whole percent and the next 0.05 dB:
+    size   worst 8.72 %  (ramp 37x53, q 100, 4:2:0, Ri 4: 1746 against 1606 bytes).  Everything above 1 % is an odd-sized 4:2:0 picture:
+           the rules code the blocks that lie wholly in the padding like any other, libjpeg codes them as copies of their DC.
+           At 64x96 and at the full-size sheet the files are within 0.5 % of PIL's.
+    PSNR   worst 0.706 dB below PIL's (edges 5x7, q 90, 4:4:4: 41.35 against 42.06 dB over 35 pixels); at 37x53 and 64x96 the worst is
+           below 0.1 dB.  174 of the 720 cases (24.2 %) have PIL's own PSNR above 50 dB and are left out: all of q = 100 without
+           subsampling, the 1x1 pictures and the grey constant.
+405 of the 720 files equal PIL's byte for byte; that is not required."""
+import io
+import os
+import re
+import sys
+import warnings
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image, JpegImagePlugin
+
+from tests import jpeg_helpers as J
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+M_SIZE = 0.09   # measured 8.72 %
+M_PSNR = 0.75   # measured 0.706 dB
+SIZES = ((1, 1), (5, 7), (37, 53), (64, 96))
+QUALITIES = (1, 50, 90, 100)
+FORMS = (("4:4:4", 3), ("4:2:0", 3), ("4:4:4", 1))
+
+
+def _pil_file(image, quality, subsampling, ri):
+    buf = io.BytesIO()
+    im = Image.fromarray(image[..., 0] if image.shape[2] == 1 else image)
+    im.save(buf, format="JPEG", quality=quality, subsampling={"4:4:4": 0, "4:2:0": 2}[subsampling], optimize=False, restart_marker_blocks=ri)
+    return buf.getvalue()
+
+
+def _open(data):
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        im = Image.open(io.BytesIO(data))
+        im.load()
+    return im
+
+
+@pytest.fixture(scope="module")
+def corpus():
+    """[(kind, H, W, quality, subsampling, C, ri, image, the helper's file)]: five contents x four sizes x four qualities x three forms x
+    Ri {none, 1, the MCUs of a row}."""
+    cases = []
+    for kind in J.KINDS:
+        for H, W in SIZES:
+            for sub, C in FORMS:
+                image = J.picture(kind, H, W, C)
+                for quality in QUALITIES:
+                    for ri in (0, 1, J.geometry(H, W, C, sub)["mcux"]):
+                        cases.append((kind, H, W, quality, sub, C, ri, image, J.encode(image, quality, sub, ri)))
+    assert len(cases) == 720
+    return cases
+
+
+def test_pil_reads_every_file(corpus):
+    for kind, H, W, quality, sub, C, ri, image, data in corpus:
+        im = _open(data)
+        assert im.size == (W, H) and im.mode == ("RGB" if C == 3 else "L"), (kind, H, W, quality, sub, C, ri)
+        assert JpegImagePlugin.get_sampling(im) == ({"4:4:4": 0, "4:2:0": 2}[sub] if C == 3 else -1)
+        assert im.info["jfif"] == 257 and im.info["jfif_version"] == (1, 1) and im.info["jfif_unit"] == 0 and im.info["jfif_density"] == (1, 1)
+
+
+@pytest.mark.parametrize("C", [1, 3])
+def test_quantisation_tables_equal_pils_at_every_quality(C):
+    image = J.picture("texture", 8, 8, C)
+    for quality in range(1, 101):
+        assert _open(J.encode(image, quality, "4:4:4")).quantization == _open(_pil_file(image, quality, "4:4:4", 0)).quantization, quality
+
+
+def test_strict_marker_parser(corpus):
+    for kind, H, W, quality, sub, C, ri, image, data in corpus:
+        info = J.parse(data)
+        assert (info["H"], info["W"], info["C"], info["dri"], info["subsampling"]) == (H, W, C, ri, sub)
+        assert info["header_bytes"] == J.file_header_bytes(C) - (0 if ri else 6)
+        assert len(data) <= J.capacity(H, W, C, sub) or ri == 0
+    # the RST count wraps: 11 intervals at Ri = 3, 27 at Ri = 1 with 4:2:0
+    assert J.parse(J.encode(J.picture("texture", 88, 24, 3), 90, "4:4:4", 3))["intervals"] == 11
+    assert J.parse(J.encode(J.picture("noise", 40, 130, 3), 50, "4:2:0", 1))["intervals"] == 27
+    # the default interval: one MCU row, cut to INTERVAL_BLOCKS blocks where a row is longer
+    info = J.parse(J.encode(J.picture("texture", 16, 2736, 3), 50, "4:2:0"))
+    assert info["dri"] == 170 and info["intervals"] == 2
+
+
+def test_parser_refuses_what_the_rules_do_not_allow():
+    data = J.encode(J.picture("noise", 37, 53, 3), 90, "4:2:0", 2)
+    J.parse(data)
+    scan_at = J.file_header_bytes(3)
+    rst = data.index(b"\xff\xd0", scan_at)
+    for bad in (data + b"\x00", data[:-2], data[:rst + 1] + b"\xd3" + data[rst + 2:], data[:rst] + data[rst + 2:],
+                data[:scan_at + 5] + b"\xff\x01" + data[scan_at + 7:], data[:2] + data[20:]):
+        with pytest.raises(AssertionError):
+            J.parse(bad)
+
+
+def test_size_and_quality_against_pils_encoder(corpus):
+    worst_size, worst_psnr, left_out = (0.0, None), (0.0, None), 0
+    for kind, H, W, quality, sub, C, ri, image, data in corpus:
+        theirs = _pil_file(image, quality, sub, ri)
+        ratio = len(data) / len(theirs) - 1.0
+        if ratio > worst_size[0]:
+            worst_size = (ratio, (kind, H, W, quality, sub, C, ri, len(data), len(theirs)))
+        mine = J.psnr(np.asarray(_open(data)).reshape(H, W, C), image)
+        pils = J.psnr(np.asarray(_open(theirs)).reshape(H, W, C), image)
+        if pils > 50.0:
+            left_out += 1
+        elif pils - mine > worst_psnr[0]:
+            worst_psnr = (pils - mine, (kind, H, W, quality, sub, C, ri, round(mine, 3), round(pils, 3)))
+    print(f"jpeg against PIL: worst size +{100 * worst_size[0]:.2f} % {worst_size[1]}; worst PSNR -{worst_psnr[0]:.3f} dB {worst_psnr[1]}; "
+          f"{left_out} of {len(corpus)} above 50 dB")
+    assert worst_size[0] <= M_SIZE, worst_size
+    assert worst_psnr[0] <= M_PSNR, worst_psnr
+    assert 4 * left_out <= len(corpus), left_out
+
+
+def test_integer_dct_against_the_float_dct():
+    blocks = np.random.default_rng(0).integers(0, 256, (20000, 8, 8))
+    k, n = np.mgrid[0:8, 0:8]
+    M = np.where(k == 0, 1.0 / np.sqrt(8.0), 0.5) * np.cos((2 * n + 1) * k * np.pi / 16.0)
+    exact = 8.0 * np.einsum("km,bmn,jn->bkj", M, blocks - 128.0, M)
+    assert np.abs(J.fdct(blocks) - exact).max() <= 1.72
+    J.fdct(np.stack([np.zeros((8, 8), int), np.full((8, 8), 255), 255 * (np.indices((8, 8)).sum(0) & 1)]))  # the helper's int32 bounds hold at the extremes
+
+
+def test_host_path_equals_the_helper(corpus):
+    from gscream_amd import jpeg
+    for kind, H, W, quality, sub, C, ri, image, data in corpus:
+        batch = jpeg.encode(torch.from_numpy(image), quality, sub, ri, cap=max(len(data), J.file_header_bytes(C)))
+        assert jpeg.last_path == "torch"
+        assert jpeg.to_bytes(batch) == [data], (kind, H, W, quality, sub, C, ri)
+        assert jpeg.capacity(H, W, C, sub) == J.capacity(H, W, C, sub)
+    # the default interval, a batch, strided panels, and a buffer too small for one of the pictures
+    images = np.stack([J.picture(k, 37, 53, 3, seed=4) for k in ("constant", "noise", "texture")])
+    want = [J.encode(im, 100) for im in images]
+    batch = jpeg.encode(torch.from_numpy(images), 100, cap=(len(want[0]) + len(want[1])) // 2)
+    words = batch.data[:, :16].numpy().copy().view("<u4")
+    assert words[:, 1].tolist() == [0, jpeg.NEED_CAPACITY, jpeg.NEED_CAPACITY] and words[:, 0].tolist() == [len(w) for w in want]
+    assert jpeg.to_bytes(batch) == want and jpeg.last_info["reencoded"] == 2
+    sheet = torch.from_numpy(np.concatenate(list(images), 1))
+    panels = sheet.view(37, 3, 53, 3).permute(1, 0, 2, 3)
+    assert jpeg.to_bytes(jpeg.encode(panels, 100, cap=jpeg.capacity(37, 53, 3))) == want and jpeg.last_info["reencoded"] == 0
+
+
+def test_committed_tables_equal_pils():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_jpeg_tables as T
+    tables = T.from_pil()
+    assert tables == J.TABLES, "gscream_amd/jpeg_tables.json differs from what PIL writes today (tools/make_jpeg_tables.py)"
+    with open(T.HEADER_PATH) as f:
+        assert f.read() == T.header_text(tables), "gscream_amd/csrc/jpeg_tables.h differs from the tables (tools/make_jpeg_tables.py)"
+    assert tables["dct"] == J.dct_matrix().tolist() and sorted(tables["zigzag"]) == list(range(64))
+    for key in ("dc0", "dc1", "ac0", "ac1"):  # complete prefix codes of at most 16 bits
+        code, length = J.huffman_codes(tables["huffman"][key])
+        used = length[length > 0]
+        assert used.max() <= 16 and (2.0 ** -used).sum() < 1.0 and len(set(zip(code[length > 0].tolist(), used.tolist()))) == used.size
+
+
+def test_mjpeg_writer_on_cpu_tensors(tmp_path):
+    from gscream_amd import jpeg, video
+    frames = torch.from_numpy(np.stack([J.picture(k, 36, 52, 3, seed=s) for s, k in enumerate(("texture", "noise", "edges", "ramp", "constant"))]))
+    path = tmp_path / "clip.avi"
+    with video.MjpegWriter(str(path), 52, 36, fps=30, quality=90) as w:
+        w.add(frames[:2])
+        w.add(frames[2])
+        w.add(frames[3:])
+    data = path.read_bytes()
+    avi = J.parse_avi(data)
+    assert (avi["width"], avi["height"], avi["scale"], avi["rate"], avi["us_per_frame"], len(avi["frames"])) == (52, 36, 1, 30, 33333, 5)
+    assert any(len(f) & 1 for f in avi["frames"]) and any(not len(f) & 1 for f in avi["frames"]), "both odd and even frame sizes: the padding rule is used"
+    for frame, got in zip(frames, avi["frames"]):
+        assert got == jpeg.to_bytes(jpeg.encode(frame, 90))[0] == J.encode(frame.numpy(), 90)
+        assert _open(got).size == (52, 36)
+    # the sheets' line: an iterator of pictures, 4:4:4 where a size is odd
+    odd = tmp_path / "odd.avi"
+    assert video.save_rgbd_video((torch.from_numpy(J.picture("texture", 35, 52, 3, seed=s)) for s in range(3)), str(odd), batch=2) == 3
+    avi = J.parse_avi(odd.read_bytes())
+    assert avi["fps"] == 25 and [J.parse(f)["subsampling"] for f in avi["frames"]] == ["4:4:4"] * 3
+
+
+def test_argument_errors_raise_before_any_work(tmp_path):
+    from gscream_amd import jpeg, video
+    ok = torch.zeros(8, 8, 3, dtype=torch.uint8)
+    for call in (lambda: jpeg.encode(torch.zeros(8, 8, 4, dtype=torch.uint8)), lambda: jpeg.encode(ok, quality=0), lambda: jpeg.encode(ok, quality=101),
+                 lambda: jpeg.encode(torch.zeros(8, 8, 1, dtype=torch.uint8), subsampling="4:2:0"), lambda: jpeg.encode(ok, subsampling="4:2:2"),
+                 lambda: jpeg.encode(ok, restart_interval=171), lambda: jpeg.encode(ok, subsampling="4:4:4", restart_interval=342),
+                 lambda: jpeg.encode(ok, cap=100), lambda: jpeg.encode(torch.zeros(0, 8, 3, dtype=torch.uint8)),
+                 lambda: jpeg.encode(ok, out=torch.zeros(1, 700, dtype=torch.uint8)[:, :650])):
+        with pytest.raises(ValueError):
+            call()
+    with pytest.raises(TypeError):
+        jpeg.encode(ok.float())
+    path = tmp_path / "never.avi"
+    for kw in (dict(W=53, H=36), dict(W=52, H=35), dict(W=52, H=36, fps=0), dict(W=52, H=36, quality=0), dict(W=52, H=36, subsampling="4:1:1")):
+        with pytest.raises(ValueError):
+            video.MjpegWriter(str(path), **kw)
+    assert not path.exists(), "a refused writer must not create the file"
+    with video.MjpegWriter(str(path), 52, 35, subsampling="4:4:4") as w:  # odd sizes are fine without subsampling
+        with pytest.raises(ValueError):
+            w.add(torch.zeros(36, 52, 3, dtype=torch.uint8))
+    assert J.parse_avi(path.read_bytes())["frames"] == []
+
+
+def test_native_declarations(native_lib):
+    """The three entry points are declared in the header the way gsr_png_encode is (the arena's proxy reads pointer and const from
+    it), exported and bound; the ABI version stays."""
+    from tests import arena_helpers as A
+    from gscream_amd import _native
+    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
+    assert re.search(r"#define\s+GSR_ABI_VERSION\s+8\b", hdr) and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    table = A.header_table()
+    for name in ("gsr_jpeg_capacity", "gsr_jpeg_workspace_bytes", "gsr_jpeg_encode"):
+        assert name in table and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
+    params = {p[1]: p for p in table["gsr_jpeg_encode"]}
+    assert params["images"][2:] == (True, True) and params["out"][2:] == (True, False) and params["workspace"][2:] == (True, False)
+    assert len(table["gsr_jpeg_encode"]) == len(native_lib.gsr_jpeg_encode.argtypes)
+    for name, value in (("GSR_JPEG_HEADER_BYTES", _native.JPEG_HEADER_BYTES), ("GSR_JPEG_INTERVAL_BLOCKS", _native.JPEG_INTERVAL_BLOCKS),
+                        ("GSR_JPEG_NEED_CAPACITY", _native.JPEG_NEED_CAPACITY)):
+        assert re.search(rf"#define\s+{name}\s+{value}\b", hdr)
+    # the capacity and the rejections that need no device
+    for H, W, C, sub in ((1, 1, 1, "4:4:4"), (37, 53, 3, "4:2:0"), (567, 4032, 3, "4:4:4"), (567, 4032, 3, "4:2:0")):
+        assert native_lib.gsr_jpeg_capacity(H, W, C, int(sub.replace(":", ""))) == J.capacity(H, W, C, sub)
+    for args in ((0, 8, 3, 444), (8, 8, 4, 444), (8, 8, 1, 420), (8, 8, 3, 422), (65536, 8, 3, 444), (65535, 65535, 1, 444)):
+        assert native_lib.gsr_jpeg_capacity(*args) == 0
+    assert native_lib.gsr_jpeg_workspace_bytes(1, 8, 8, 3, 420, 171) == 0 and native_lib.gsr_jpeg_workspace_bytes(1, 8, 8, 3, 420, 170) > 0
+    assert native_lib.gsr_jpeg_encode(None, 24, 0, 1, 8, 8, 3, 95, 444, 0, None, 1024, None, None) != 0
