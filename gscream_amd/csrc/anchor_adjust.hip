@@ -90,27 +90,20 @@ __global__ void __launch_bounds__(GAA_THREADS) gaa_place_kernel(int N, const uin
 struct GaaWork {
     unsigned long long* block_sum;  // [blocks(N) + 1]
     uint8_t* keep;                  // [N]
+    size_t bytes;
 };
 
-static GaaWork gaa_carve(void* base, int N, size_t* bytes)
+static GaaWork gaa_carve(void* base, int N)
 {
     GaaWork w{};
-    char* p = (char*)base;
-    size_t off = 0;
-    w.block_sum = (unsigned long long*)(p + off);
-    off += gsr_align((size_t)(gaa_blocks(N, GAA_THREADS) + 1) * 8);
-    w.keep = (uint8_t*)(p + off);
-    off += gsr_align((size_t)N);
-    if (bytes) *bytes = off;
+    GsrCarver c(base);
+    w.block_sum = c.take<unsigned long long>((size_t)gaa_blocks(N, GAA_THREADS) + 1);
+    w.keep = c.take<uint8_t>((size_t)N);
+    w.bytes = c.total();
     return w;
 }
 
-size_t gaa_workspace_bytes(int N)
-{
-    size_t b = 0;
-    (void)gaa_carve(nullptr, N, &b);
-    return b;
-}
+size_t gaa_workspace_bytes(int N) { return gaa_carve(nullptr, N).bytes; }
 
 hipError_t gaa_launch_offsets(int L0, const float* accum, const float* denom, float thr_half, float* grads_norm, uint8_t* offset_mask,
                               hipStream_t stream)
@@ -125,7 +118,7 @@ hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* ancho
                            void* workspace, int32_t* keep_rows, uint8_t* reset, int32_t* info, hipStream_t stream)
 {
     if (N == 0) return hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream);
-    const GaaWork w = gaa_carve(workspace, N, nullptr);
+    const GaaWork w = gaa_carve(workspace, N);
     const int nb = gaa_blocks(N, GAA_THREADS);
     hipLaunchKernelGGL(gaa_flag_kernel, dim3(nb), dim3(GAA_THREADS), 0, stream, N, opacity_accum, anchor_demon, prune_mask, min_opacity, thr,
                        w.keep, reset, w.block_sum);

@@ -266,6 +266,7 @@ struct GagWork {
     uint32_t* pos_seg;              // [L]
     int32_t* seg_slot;              // [L]
     uint32_t cap;
+    size_t bytes;
 };
 
 static uint32_t gag_capacity(int N)
@@ -275,39 +276,27 @@ static uint32_t gag_capacity(int N)
     return cap;
 }
 
-static GagWork gag_carve(void* base, int N, int L, size_t* bytes)
+static GagWork gag_carve(void* base, int N, int L)
 {
     GagWork w{};
-    char* p = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     w.cap = gag_capacity(N);
-    w.cells = (int32_t*)(p + off);
-    off += gsr_align((size_t)3 * N * 4);
-    w.table = (int32_t*)(p + off);
-    off += gsr_align((size_t)w.cap * 4);
-    w.block_sum = (unsigned long long*)(p + off);
-    off += gsr_align((size_t)(gag_blocks(L) + 1) * 8);
-    w.head_kind = (uint8_t*)(p + off);
-    off += gsr_align((size_t)L);
-    w.pos_seg = (uint32_t*)(p + off);
-    off += gsr_align((size_t)L * 4);
-    w.seg_slot = (int32_t*)(p + off);
-    off += gsr_align((size_t)L * 4);
-    if (bytes) *bytes = off;
+    w.cells = c.take<int32_t>((size_t)3 * N);
+    w.table = c.take<int32_t>(w.cap);
+    w.block_sum = c.take<unsigned long long>((size_t)gag_blocks(L) + 1);
+    w.head_kind = c.take<uint8_t>((size_t)L);
+    w.pos_seg = c.take<uint32_t>((size_t)L);
+    w.seg_slot = c.take<int32_t>((size_t)L);
+    w.bytes = c.total();
     return w;
 }
 
-size_t gag_workspace_bytes(int N, int L)
-{
-    size_t b = 0;
-    (void)gag_carve(nullptr, N, L, &b);
-    return b;
-}
+size_t gag_workspace_bytes(int N, int L) { return gag_carve(nullptr, N, L).bytes; }
 
 hipError_t gag_launch_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling, const uint8_t* mask, float inv,
                            void* workspace, int64_t* keys, int32_t* rows, int32_t* info, hipStream_t stream)
 {
-    const GagWork w = gag_carve(workspace, N, L, nullptr);
+    const GagWork w = gag_carve(workspace, N, L);
     hipError_t e;
     if ((e = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.table, 0xff, (size_t)w.cap * 4, stream)) != hipSuccess) return e;
@@ -329,7 +318,7 @@ hipError_t gag_launch_emit(int N, int K, int F, int L, int M, const float* feat,
                            const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor, float* new_feat, int32_t* info,
                            hipStream_t stream)
 {
-    const GagWork w = gag_carve(workspace, N, L, nullptr);
+    const GagWork w = gag_carve(workspace, N, L);
     hipError_t e;
     if ((e = hipMemsetAsync(info + 2, 0, sizeof(int32_t), stream)) != hipSuccess) return e;
     if (M <= 0) return hipSuccess;

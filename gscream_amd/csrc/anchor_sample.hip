@@ -271,34 +271,27 @@ struct GasWork {
     unsigned long long* sum_bg;  // [blocks(N) + 1]
     uint8_t* cls;                // [N]
     uint8_t* flag;               // [N]
+    size_t bytes;
 };
 
-static GasWork gas_carve(void* base, int N, size_t* bytes)
+static GasWork gas_carve(void* base, int N)
 {
     GasWork w{};
-    char* p = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t nb = (size_t)gas_blocks(N, GAS_THREADS) + 1;
-    w.head = (uint32_t*)(p + off);
-    off += gsr_align((size_t)GAS_HEAD_WORDS * 4);
-    w.sum_fg = (unsigned long long*)(p + off);
-    off += gsr_align(nb * 8);
-    w.sum_bg = (unsigned long long*)(p + off);
-    off += gsr_align(nb * 8);
-    w.cls = (uint8_t*)(p + off);
-    off += gsr_align((size_t)N);
-    w.flag = (uint8_t*)(p + off);
-    off += gsr_align((size_t)N);
-    if (bytes) *bytes = off;
+    w.head = c.take<uint32_t>(GAS_HEAD_WORDS);
+    w.sum_fg = c.take<unsigned long long>(nb);
+    w.sum_bg = c.take<unsigned long long>(nb);
+    w.cls = c.take<uint8_t>((size_t)N);
+    w.flag = c.take<uint8_t>((size_t)N);
+    w.bytes = c.total();
     return w;
 }
 
 size_t gas_workspace_bytes(int N, int max_pairs)
 {
     (void)max_pairs;  // the row lists are the caller's; the argument keeps the size query's signature in step with the call's
-    size_t b = 0;
-    (void)gas_carve(nullptr, N, &b);
-    return b;
+    return gas_carve(nullptr, N).bytes;
 }
 
 hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask, int min_y,
@@ -307,7 +300,7 @@ hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* 
 {
     hipError_t e;
     if (N == 0) return hipMemsetAsync(info, 0, 8 * sizeof(int32_t), stream);
-    const GasWork w = gas_carve(workspace, N, nullptr);
+    const GasWork w = gas_carve(workspace, N);
     const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
     const int nt = gas_blocks(N, GAS_TILE), nb = gas_blocks(N, GAS_THREADS);
     if ((e = hipMemsetAsync(w.head, 0, (size_t)GAS_HEAD_WORDS * 4, stream)) != hipSuccess) return e;

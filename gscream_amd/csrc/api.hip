@@ -125,12 +125,7 @@ extern "C" int gsr_device_count(void)
 extern "C" size_t gsr_geom_bytes(int P) { return gsr_carve_geom(nullptr, P).bytes; }
 extern "C" size_t gsr_image_bytes(int P, int W, int H) { return gsr_carve_image(nullptr, P, W, H).bytes; }
 extern "C" size_t gsr_binning_bytes(int R) { return gsr_carve_binning(nullptr, R).bytes; }
-extern "C" size_t gsr_backward_scratch_bytes(int P, int num_slots)
-{
-    // slots[num_slots], 48 B each, + the per-Gaussian backward's list of heavy 64-Gaussian groups (count + indices)
-    return gsr_align((size_t)(num_slots > 0 ? num_slots : 1) * GSR_SLOT_FLOATS * sizeof(float)) +
-           gsr_align(((size_t)(P > 0 ? P : 1) / 64 + 18) * sizeof(uint32_t));
-}
+extern "C" size_t gsr_backward_scratch_bytes(int P, int num_slots) { return gsr_carve_backward_scratch(nullptr, P, num_slots).bytes; }
 
 static bool gsr_partial_sort(const gsr_tuning* tuning) { return !(tuning && tuning->disable_partial_sort); }
 static bool gsr_inference(const gsr_tuning* tuning) { return tuning && tuning->inference; }
@@ -173,6 +168,7 @@ static int gsr_check_dims(int P, int W, int H)
     if (gx > 65535 || gy > 65535) return gsr_fail(GSR_ERR_UNSUPPORTED, "image too large: %ldx%ld tiles", gx, gy);
     // more than GSR_MAX_TILES_LDS tiles: supported through the global-counter binning fallback (binning.hip)
     if (gx * gy > (1L << 24)) return gsr_fail(GSR_ERR_UNSUPPORTED, "image too large: %ld tiles", gx * gy);
+    // (no accepted size wraps a carve, GsrCarver::ok(): at most 2^24 tiles = 2^32 pixels of 648 checkpoint bytes, P and R below 2^31 of 64 B)
     return GSR_OK;
 }
 
@@ -585,9 +581,9 @@ extern "C" int gsr_backward(int P, int D, int M, int W, int H, int R, int binnin
 
     const GsrCam cam = gsr_make_cam(W, H, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier);
     const GsrFrame f = gsr_make_frame(P, W, H, geom_ws, image_ws, binning_ws, binning_capacity, debug, stream);
-    float* slots = (float*)scratch;
-    // heavy[0] = number of heavy groups (zeroed by the backward blend, which always runs first), heavy[16..] = their indices
-    uint32_t* heavy = (uint32_t*)((char*)scratch + gsr_align((size_t)(R > 0 ? R : 1) * GSR_SLOT_FLOATS * sizeof(float)));
+    const GsrBackwardScratch sc = gsr_carve_backward_scratch(scratch, P, R);
+    float* slots = sc.slots;
+    uint32_t* heavy = sc.heavy;
     // written-slot flags: cleared by the forward's tile sort, set by the backward blend; the set of written slots is a function
     // of the forward state alone, so a second backward over the same forward state finds exactly the flags it would set
     uint8_t* slot_written = f.bin.slot_written;
@@ -658,6 +654,7 @@ static int gsr_check_loss_args(int C, int H, int W, const float* img, const floa
 {
     if (C < 1 || H < 1 || W < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: C, H, W must be >= 1 (got %d, %d, %d)", C, H, W);
     if ((long long)C * H * W > 0x7fffffffLL) return gsr_fail(GSR_ERR_UNSUPPORTED, "loss: image too large");
+    // (no accepted size wraps the carve: three planes of C*H*W floats, below 2^35 bytes)
     if (!img || !gt || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: a required pointer is NULL");
     return GSR_OK;
 }
@@ -725,7 +722,7 @@ extern "C" int gsr_knn_mean_dist2(int P, const float* points, float* mean_dist2,
 }
 
 // ---- scene initialisation (scene_init.hip) ----
-#define GSI_MAX_N (1 << 30)
+#define GSI_MAX_N (1 << 30)  // (no accepted N wraps a carve: the largest piece is N keys of 8 bytes = 2^33)
 extern "C" int gsr_sort_block_keys(void) { return GSR_SORT_BLOCK_KEYS; }
 
 extern "C" size_t gsr_sort_keys_workspace_bytes(int N) { return N < 0 || N > GSI_MAX_N ? 0 : gsi_sort_workspace_bytes(N); }
@@ -919,6 +916,7 @@ static int gag_check_sizes(const char* what, int N, int K, int L)
 {
     if (N < 0 || K < 1 || L < 0 || (long long)L > (long long)N * K || L > 0x7fffff00)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes N=%d K=%d L=%d (need 0 <= L <= N*K < 2^31)", what, N, K, L);
+    // (no accepted size wraps the carve: 3 N cells and L slots of 4 bytes, below 2^35)
     return GSR_OK;
 }
 
@@ -964,6 +962,7 @@ static int gca_check_sizes(const char* what, int B, int H, int I, int J, int dim
     if (dim_head != 64) return gsr_fail(GSR_ERR_UNSUPPORTED, "%s: dim_head = %d (this path is built for 64)", what, dim_head);
     if (B < 1 || H < 1 || I < 1 || J < 1 || (long long)B * H > 65535 || (long long)B * H * ((long long)I + J) * 64 > 0x7fffffffLL)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes b=%d heads=%d i=%d j=%d", what, B, H, I, J);
+    // (no accepted size wraps the carve: B*H*(I + J) < 2^25 rows of 12 bytes)
     return GSR_OK;
 }
 
@@ -1006,6 +1005,7 @@ static int gas_check_sizes(int N, int H, int W, int max_pairs)
 {
     if (N < 0 || N > 0x7fffff00 || max_pairs < 0 || H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || (long long)H * W > 0x7fffffffLL)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor sample: bad sizes N=%d H=%d W=%d max_pairs=%d", N, H, W, max_pairs);
+    // (no accepted size wraps the carve: N < 2^31 bytes per array)
     return GSR_OK;
 }
 
@@ -1032,7 +1032,7 @@ extern "C" int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, co
 // ---- anchor pruning (anchor_adjust.hip) ----
 extern "C" size_t gsr_anchor_adjust_workspace_bytes(int N)
 {
-    if (N < 0 || N > 0x7fffff00) return 0;
+    if (N < 0 || N > 0x7fffff00) return 0;  // (no accepted N wraps the carve: N bytes + N / 256 sums)
     return gaa_workspace_bytes(N);
 }
 
@@ -1140,14 +1140,14 @@ static int metrics_check_sizes(int B, int C, int H, int W)
     if (H < 3 || W < 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: H=%d W=%d (need both >= 3: reflect padding of 2)", H, W);
     if ((double)C * (double)H * (double)W >= 2147483392.0)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: C=%d H=%d W=%d has too many elements (need C*H*W < 2^31 - 256)", C, H, W);
+    // (no accepted size wraps the carve: 65535 planes of fewer than 2^22 tiles, 64 bytes each)
     return GSR_OK;
 }
 
 extern "C" size_t gsr_image_metrics_workspace_bytes(int B, int C, int H, int W)
 {
     if (metrics_check_sizes(B, C, H, W)) return 0;
-    const size_t tiles = (size_t)((W + METRICS_TILE_W - 1) / METRICS_TILE_W) * (size_t)((H + METRICS_TILE_H - 1) / METRICS_TILE_H);
-    return (size_t)B * (size_t)C * tiles * 8 * sizeof(double);
+    return metrics_workspace_bytes(B, C, H, W);
 }
 
 extern "C" int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
@@ -1175,6 +1175,7 @@ static int lpips_check_sizes(int B, int H, int W)
     if (H < 16 || W < 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d (need both >= 16: four 2x2 pools)", H, W);
     if ((int64_t)H * (int64_t)W >= 0x7fffff00LL)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d has too many pixels (need H*W < 2^31 - 256)", H, W);
+    // (no accepted size wraps the carve: an activation buffer is 2 B * 64 * H*W floats < 2^15 * 2^9 * 2^31 = 2^55 bytes)
     return GSR_OK;
 }
 
@@ -1222,14 +1223,14 @@ static int frames_check_sizes(const char* what, int B, int H, int W)
     if (B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: B=%d has too many frames (need B <= 65535)", what, B);
     if ((int64_t)H * (int64_t)W >= 0x7fffff00LL / 4)  // (H*W*4 itself can pass 2^63)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d has too many pixels (need H*W*4 < 2^31 - 256)", what, H, W);
+    // (no accepted size wraps the carve: 65535 frames of fewer than 2^17 chunks, 64 bytes each)
     return GSR_OK;
 }
 
 extern "C" size_t gsr_frame_stats_workspace_bytes(int B, int H, int W)
 {
     if (frames_check_sizes("frame stats", B, H, W)) return 0;
-    const size_t chunks = ((size_t)H * (size_t)W + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK;
-    return (size_t)B * chunks * 8 * sizeof(double);
+    return frames_stats_workspace_bytes(B, H, W);
 }
 
 extern "C" int gsr_frame_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
@@ -1291,6 +1292,7 @@ static int png_check_sizes(int B, int H, int W, int C)
     if ((int64_t)W * C >= (1 << 24)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: W=%d C=%d has too long a row (need W*C < 2^24)", W, C);
     if ((int64_t)H * ((int64_t)W * C + 1) >= 0x70000000LL)
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: H=%d W=%d C=%d has too many bytes (need H*(1 + W*C) < 0x70000000)", H, W, C);
+    // (no accepted size wraps the layout: a picture's part is below 2^32 bytes, B below 2^16)
     return GSR_OK;
 }
 
@@ -1329,6 +1331,7 @@ static int jpeg_check_sizes(int B, int H, int W, int C, int subsampling)
     if (subsampling == 420 && C == 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: subsampling 420 with C=1 (a grey picture has no chroma)");
     if (jpeg_layout(H, W, C, subsampling, 0).capacity >= ((size_t)1 << 31))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: H=%d W=%d C=%d has a capacity of 2^31 bytes or more", H, W, C);
+    // (no accepted size wraps the layout: a picture's part is below 2^32 bytes, B below 2^16)
     return GSR_OK;
 }
 
@@ -1388,7 +1391,7 @@ extern "C" int gsr_jpeg_encode(const uint8_t* images, long long row_stride, long
 // ---- PNG decoding (png_decode.hip) ----
 extern "C" size_t gsr_png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces)
 {
-    if (nfiles <= 0 || npieces <= 0 || stream_bytes >= ((size_t)1 << 40)) return 0;
+    if (nfiles <= 0 || npieces <= 0 || stream_bytes >= ((size_t)1 << 40)) return 0;  // (no accepted size wraps the carve: 2^40 + 2^31 * 12 + 2^31 * 4)
     return png_decode_workspace_bytes(stream_bytes, nfiles, npieces);
 }
 
@@ -1403,7 +1406,7 @@ extern "C" int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png
     if (((uintptr_t)bytes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)files & 7) || ((uintptr_t)pieces & 7) ||
         ((uintptr_t)status & 3))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: bytes, out and workspace are 16-byte aligned, the tables 8, status 4");
-    if (workspace_bytes < (size_t)npieces * 12 + (size_t)nfiles * 4)
+    if (workspace_bytes < pd_tables_bytes(nfiles, npieces))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
     GSR_HIP(png_launch_decode(bytes, nbytes, files, nfiles, pieces, npieces, verify_crc, out, out_bytes, status, workspace, workspace_bytes,
                               (hipStream_t)stream),

@@ -884,6 +884,7 @@ __global__ void __launch_bounds__(1024) gsr_tile_sort_global_kernel(const uint2*
 // Dynamic LDS beyond 64 KiB needs a one-time opt-in per kernel and device (kept out of the per-call path: a
 // hipFuncSetAttribute between the stage-1 read-back and the stage-2 launches is exposed GPU idle time).
 constexpr size_t GSR_BIG_LDS = 160 * 1024 - 8192;  // static LDS: hist / scatter 2 KiB, tile sort 4.2 KiB (bucket offsets)
+static inline size_t gsr_lds_round(size_t x) { return (x + 255) & ~(size_t)255; }  // dynamic LDS sizes in whole 256-byte steps
 
 // The scatter's dynamic LDS for a band of tb tiles: the three per-tile arrays (fixed) + a staging buffer of 10 B per instance, as
 // much as the CU has left (stage_cap instances; 0 = no room worth staging in).  gsr_scatter_bands chooses the band count by it
@@ -892,7 +893,7 @@ struct GsrScatterLds { size_t fixed, stage_cap; };
 static GsrScatterLds gsr_scatter_lds(size_t tb)
 {
     const size_t budget = GSR_BIG_LDS - 1024;  // static arrays of the kernel: ~4.3 KiB
-    const size_t fixed = gsr_align(tb * 12 + 8);
+    const size_t fixed = gsr_lds_round(tb * 12 + 8);
     return { fixed, budget > fixed + 4096 ? (budget - fixed) / 10 : 0 };
 }
 
@@ -942,7 +943,7 @@ hipError_t gsr_launch_count(const GsrFrame& f, uint32_t* info_host_mapped, bool 
         if (e != hipSuccess) return e;
         if (occlusion_cut) {  // (api.hip enables it only up to GSR_OCC_MAX_TILES: the cut-off table sits behind the counters in LDS)
             hipLaunchKernelGGL(gsr_occ_cut_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, T, image.occ_mass, image.occ_cut);
-            hipLaunchKernelGGL((gsr_tile_hist_kernel<false, true>), dim3(nchunks), dim3(GSR_HIST_THREADS), gsr_align((size_t)T * 5), stream, P, T, gx,
+            hipLaunchKernelGGL((gsr_tile_hist_kernel<false, true>), dim3(nchunks), dim3(GSR_HIST_THREADS), gsr_lds_round((size_t)T * 5), stream, P, T, gx,
                                nchunks, geom.rect, geom.tmask, image.table, geom.scan_sums, oc);
         } else
         hipLaunchKernelGGL((gsr_tile_hist_kernel<false, false>), dim3(nchunks), dim3(GSR_HIST_THREADS), (size_t)T * 4, stream, P, T, gx,
@@ -1045,7 +1046,7 @@ static GsrBinning gsr_sort_binning(const GsrBinning& bin_in, bool inference)
 static void gsr_launch_sort_lds(int T, int capacity, uint32_t lo, uint32_t cap, uint32_t longest, const GsrImage& image, const GsrBinning& bin,
                                 const uint32_t* only_flagged, uint32_t* sorted_len, hipStream_t stream)
 {
-    const size_t lds = gsr_align((size_t)GSR_PAD(longest) * 8 + 8);
+    const size_t lds = gsr_lds_round((size_t)GSR_PAD(longest) * 8 + 8);
     if (longest <= 2048u)
         hipLaunchKernelGGL(gsr_tile_sort_lds_kernel<256>, dim3(T), dim3(256), lds, stream, image.ranges, bin.seg_keys,
                            bin.point_list, bin.slot_written, lo, cap, longest, (uint32_t)capacity, only_flagged, sorted_len);

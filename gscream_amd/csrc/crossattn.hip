@@ -368,27 +368,31 @@ __global__ __launch_bounds__(GCA_THREADS) void gca_backward_kernel(GcaArgs a)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-static size_t gca_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // workspace: stats of x rows, stats of context rows (float2 each), then the two backward row-dot arrays (float)
-size_t gca_workspace_bytes(int B, int H, int I, int J)
+struct GcaWork { float2* stats[2]; float* dot[2]; size_t bytes; };
+static GcaWork gca_carve(void* base, int B, int H, int I, int J)
 {
+    GcaWork w{};
+    GsrCarver c(base);
     const size_t bh = (size_t)B * H;
-    return gca_align(bh * I * sizeof(float2)) + gca_align(bh * J * sizeof(float2)) + gca_align(bh * I * sizeof(float)) + gca_align(bh * J * sizeof(float));
+    w.stats[0] = c.take<float2>(bh * I);
+    w.stats[1] = c.take<float2>(bh * J);
+    w.dot[0] = c.take<float>(bh * I);
+    w.dot[1] = c.take<float>(bh * J);
+    w.bytes = c.total();
+    return w;
 }
+
+size_t gca_workspace_bytes(int B, int H, int I, int J) { return gca_carve(nullptr, B, H, I, J).bytes; }
 
 static GcaArgs gca_args(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv, const uint8_t* mask,
                         const uint8_t* cmask, float scale, void* workspace)
 {
     GcaArgs a = {};
-    const size_t bh = (size_t)B * H;
-    char* w = static_cast<char*>(workspace);
+    const GcaWork w = gca_carve(workspace, B, H, I, J);
     a.s[0].qk = qk; a.s[0].v = v; a.s[0].mask = mask; a.s[0].n = I;
     a.s[1].qk = cqk; a.s[1].v = cv; a.s[1].mask = cmask; a.s[1].n = J;
-    a.s[0].stats = reinterpret_cast<float2*>(w); w += gca_align(bh * I * sizeof(float2));
-    a.s[1].stats = reinterpret_cast<float2*>(w); w += gca_align(bh * J * sizeof(float2));
-    a.s[0].dot = reinterpret_cast<float*>(w); w += gca_align(bh * I * sizeof(float));
-    a.s[1].dot = reinterpret_cast<float*>(w);
+    for (int k = 0; k < 2; k++) { a.s[k].stats = w.stats[k]; a.s[k].dot = w.dot[k]; }
     a.B = B; a.H = H; a.scale = scale;
     return a;
 }

@@ -231,14 +231,13 @@ struct GdlWorkspace {
 static GdlWorkspace gdl_carve(void* base, int H, int W)
 {
     GdlWorkspace w;
-    char* b = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t n = (size_t)(H > 0 ? H : 1) * (W > 0 ? W : 1);
-    w.G = (float*)(b + off); off += gsr_align(n * 4);
-    w.part1 = (double*)(b + off); off += gsr_align((size_t)GDL_BLOCKS * (5 + GDL_SCALES) * 8);
-    w.part2 = (double*)(b + off); off += gsr_align((size_t)GDL_BLOCKS * (3 + GDL_SCALES) * 8);
-    w.params = (GdlParams*)(b + off); off += gsr_align(sizeof(GdlParams));
-    w.bytes = off;
+    w.G = c.take<float>(n);
+    w.part1 = c.take<double>((size_t)GDL_BLOCKS * (5 + GDL_SCALES));
+    w.part2 = c.take<double>((size_t)GDL_BLOCKS * (3 + GDL_SCALES));
+    w.params = c.take<GdlParams>(1);
+    w.bytes = c.total();
     return w;
 }
 size_t gdl_workspace_bytes(int H, int W) { return gdl_carve(nullptr, H, W).bytes; }

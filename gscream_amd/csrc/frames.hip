@@ -147,12 +147,24 @@ __global__ void __launch_bounds__(FRM_THREADS) frame_stats_finish_kernel(int chu
     p[4] = p[5] = p[6] = p[7] = 0.0f;
 }
 
+// partials[(b*chunks + chunk)*8]: the eight doubles of each chunk, nothing between them
+struct FrmStatsWork { double* partials; int chunks; size_t bytes; };
+static FrmStatsWork frm_stats_carve(void* base, int B, int H, int W)
+{
+    GsrCarver c(base);
+    const int chunks = (int)(((size_t)H * (size_t)W + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK);
+    double* partials = c.take<double>((size_t)B * (size_t)chunks * 8, sizeof(double));
+    return { partials, chunks, c.total() };
+}
+size_t frames_stats_workspace_bytes(int B, int H, int W) { return frm_stats_carve(nullptr, B, H, W).bytes; }
+
 hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
                                double* stats, float* params, hipStream_t stream)
 {
     const int HW = H * W;  // < 2^29
-    const int chunks = (HW + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK;
-    double* partials = (double*)workspace;
+    const FrmStatsWork w = frm_stats_carve(workspace, B, H, W);
+    const int chunks = w.chunks;
+    double* const partials = w.partials;
     const dim3 grid((uint32_t)chunks, (uint32_t)B);
     hipLaunchKernelGGL(frame_stats_partial_kernel<1>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, lsq_mask, (const float*)nullptr, partials);
     hipError_t e = hipGetLastError();

@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/gsraster.h"
+#include "gsr_carve.h"
 
 #define GSR_TILE 16
 // (plain #defines where gscream_amd/_layout.py mirrors the value: a -D of one of them collides instead of building a library the mirror mis-decodes)
@@ -176,8 +177,6 @@ struct GsrRec {
 };
 static_assert(sizeof(GsrRec) == 64, "one record per 64-byte line");
 
-static inline size_t gsr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct GsrGeom {
     GsrRec* rec;
     uint2* rect;
@@ -249,38 +248,36 @@ static inline GsrGrid gsr_tile_grid(int W, int H) { return { (W + GSR_TILE - 1) 
 static inline GsrGeom gsr_carve_geom(void* base, int P)
 {
     GsrGeom g;
-    size_t off = 0;
-    char* b = (char*)base;
+    GsrCarver c(base);
     size_t p = (size_t)(P > 0 ? P : 1);
-    g.rec = (GsrRec*)(b + off); off += gsr_align(p * sizeof(GsrRec));
-    g.rect = (uint2*)(b + off); off += gsr_align(p * sizeof(uint2));
-    g.depthkey = (uint32_t*)(b + off); off += gsr_align(p * 4);
-    g.tiles = (uint32_t*)(b + off); off += gsr_align(p * 4);
-    g.offsets = (uint32_t*)(b + off); off += gsr_align(p * 4);
-    g.tmask = (unsigned long long*)(b + off); off += gsr_align(p * 8);
-    g.clamped = (uint8_t*)(b + off); off += gsr_align(p * 3);
-    g.scan_sums = (uint32_t*)(b + off); off += gsr_align((size_t)(GSR_MAX_CHUNKS + 1) * 4);  // per-chunk instance totals (gsr_num_chunks(P) <= GSR_MAX_CHUNKS)
-    g.bytes = off;
+    g.rec = c.take<GsrRec>(p);
+    g.rect = c.take<uint2>(p);
+    g.depthkey = c.take<uint32_t>(p);
+    g.tiles = c.take<uint32_t>(p);
+    g.offsets = c.take<uint32_t>(p);
+    g.tmask = c.take<unsigned long long>(p);
+    g.clamped = c.take<uint8_t>(p * 3);
+    g.scan_sums = c.take<uint32_t>(GSR_MAX_CHUNKS + 1);  // per-chunk instance totals (gsr_num_chunks(P) <= GSR_MAX_CHUNKS)
+    g.bytes = c.total();
     return g;
 }
 
 static inline GsrImage gsr_carve_image(void* base, int P, int W, int H)
 {
     GsrImage im;
-    size_t off = 0;
-    char* b = (char*)base;
+    GsrCarver c(base);
     const GsrGrid grid = gsr_tile_grid(W, H);
     size_t gx = grid.gx, gy = grid.gy;
     size_t T = gx * gy > 0 ? gx * gy : 1, N = (size_t)W * H > 0 ? (size_t)W * H : 1;
-    im.ranges = (uint2*)(b + off); off += gsr_align(T * sizeof(uint2));
-    im.final_T = (float*)(b + off); off += gsr_align(N * 4);
-    im.n_contrib = (uint32_t*)(b + off); off += gsr_align(N * 4);
+    im.ranges = c.take<uint2>(T);
+    im.final_T = c.take<float>(N);
+    im.n_contrib = c.take<uint32_t>(N);
     // [chunks][T] count table; beyond the LDS tile limit (global-counter fallback) only T cursor words are needed
-    im.table = (uint32_t*)(b + off); off += gsr_align((T > GSR_MAX_TILES_LDS ? (size_t)1 : (size_t)gsr_num_chunks(P)) * T * 4);
-    im.tile_count = (uint32_t*)(b + off); off += gsr_align(T * 4);
-    im.tile_work = (uint32_t*)(b + off); off += gsr_align(T * 4);
-    im.sorted_len = (uint32_t*)(b + off); off += gsr_align(T * 4);
-    im.need_full = (uint32_t*)(b + off); off += gsr_align(T * 4);
+    im.table = c.take<uint32_t>((T > GSR_MAX_TILES_LDS ? (size_t)1 : (size_t)gsr_num_chunks(P)) * T);
+    im.tile_count = c.take<uint32_t>(T);
+    im.tile_work = c.take<uint32_t>(T);
+    im.sorted_len = c.take<uint32_t>(T);
+    im.need_full = c.take<uint32_t>(T);
     im.N = N;
     {
         // The occlusion cut-off's mass tables (GSR_OCC_COPIES * T * GSR_OCC_BUCKETS words = 5 KB per tile) live only from the preprocess
@@ -290,31 +287,47 @@ static inline GsrImage gsr_carve_image(void* base, int P, int W, int H)
         // keeps alive (round 5).
         const size_t ck = (size_t)GSR_CKPT_PLANES * ((N + 3) & ~(size_t)3) * 4;
         const size_t oc = T <= GSR_OCC_MAX_TILES ? (size_t)GSR_OCC_COPIES * T * GSR_OCC_BUCKETS * 4 : 4;
-        im.ckpt = (float*)(b + off);
-        im.occ_mass = (uint32_t*)(b + off);
-        off += gsr_align(ck > oc ? ck : oc);
+        im.ckpt = c.alias<float>();
+        im.occ_mass = c.alias<uint32_t>();
+        c.skip(ck > oc ? ck : oc);
     }
-    im.info = (uint32_t*)(b + off); off += gsr_align(16);
-    im.qresume = (uint32_t*)(b + off); off += gsr_align(4 * T * 4);
-    im.qorder = (uint32_t*)(b + off); off += gsr_align((size_t)32 * gsr_xcd_tiles((int)T) * 4);
-    im.occ_cut = (uint32_t*)(b + off); off += gsr_align(T * 4);
-    im.occ_drop = (uint32_t*)(b + off); off += gsr_align((size_t)GSR_MAX_CHUNKS * 4);
-    im.tile_group = (uint32_t*)(b + off); off += gsr_align((T / 64 + 1) * 4);
-    im.bytes = off;
+    im.info = c.take<uint32_t>(4);
+    im.qresume = c.take<uint32_t>(4 * T);
+    im.qorder = c.take<uint32_t>((size_t)32 * gsr_xcd_tiles((int)T));
+    im.occ_cut = c.take<uint32_t>(T);
+    im.occ_drop = c.take<uint32_t>(GSR_MAX_CHUNKS);
+    im.tile_group = c.take<uint32_t>(T / 64 + 1);
+    im.bytes = c.total();
     return im;
 }
 
 static inline GsrBinning gsr_carve_binning(void* base, int R)
 {
     GsrBinning bn;
-    size_t off = 0;
-    char* b = (char*)base;
+    GsrCarver c(base);
     size_t r = (size_t)(R > 0 ? R : 1);
-    bn.seg_keys = (unsigned long long*)(b + off); off += gsr_align(r * 8);
-    bn.point_list = (uint32_t*)(b + off); off += gsr_align(r * 4);
-    bn.slot_written = (uint8_t*)(b + off); off += gsr_align(r);
-    bn.bytes = off;
+    bn.seg_keys = c.take<unsigned long long>(r);
+    bn.point_list = c.take<uint32_t>(r);
+    bn.slot_written = c.take<uint8_t>(r);
+    bn.bytes = c.total();
     return bn;
+}
+
+// scratch of the backward: slots[num_slots], 48 B each, + the per-Gaussian backward's list of heavy 64-Gaussian groups:
+// heavy[0] = number of heavy groups (zeroed by the backward blend, which always runs first), heavy[16..] = their indices
+struct GsrBackwardScratch {
+    float* slots;
+    uint32_t* heavy;
+    size_t bytes;
+};
+static inline GsrBackwardScratch gsr_carve_backward_scratch(void* base, int P, int num_slots)
+{
+    GsrBackwardScratch s;
+    GsrCarver c(base);
+    s.slots = c.take<float>((size_t)(num_slots > 0 ? num_slots : 1) * GSR_SLOT_FLOATS);
+    s.heavy = c.take<uint32_t>((size_t)(P > 0 ? P : 1) / 64 + 18);
+    s.bytes = c.total();
+    return s;
 }
 
 // ---- stage launchers implemented in the .hip files (host functions, return hipError_t) ----
@@ -487,9 +500,8 @@ hipError_t normals_launch_points(int H, int W, const float* depth, const float* 
 hipError_t normals_launch_fit(int H, int W, const float* points, int size, float gamma, double eps, float* normals, hipStream_t stream);
 
 // metrics.hip: per-image L1 / MSE / PSNR / 5x5 reflect-padded SSIM, plain and masked (validated by the caller).  One workgroup per
-// METRICS_TILE_H x METRICS_TILE_W tile of a plane writes eight fp64 partial sums: the workspace is B*C*tiles*8 doubles.
-#define METRICS_TILE_W 32
-#define METRICS_TILE_H 16
+// 16 x 32 tile of a plane writes eight fp64 partial sums: the workspace is B*C*tiles*8 doubles.
+size_t metrics_workspace_bytes(int B, int C, int H, int W);
 hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
                           long long mask_stride_c, int flags, const double taps[3] /* g_0, g_1, g_2 of the window */, void* workspace,
                           double* sums, float* metrics, hipStream_t stream);
@@ -509,6 +521,7 @@ hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1,
 // eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}: the workspace is B*chunks*8 doubles, used again by the second pass (lo2 / hi2).
 // Compose: `dwords` = whole-dword stores (the caller has checked out's alignment and channels_out == 4 or W_out % 4 == 0).
 #define FRAME_STATS_CHUNK 4096
+size_t frames_stats_workspace_bytes(int B, int H, int W);
 hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
                                double* stats, float* params, hipStream_t stream);
 hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
@@ -553,6 +566,7 @@ hipError_t jpeg_launch_encode(const uint8_t* images, long long row_stride, long 
 // The workspace holds the files' inflated streams, then per piece {size, flag, offset} of the segment that starts there, then per
 // file the Adler-32 of its trailer.
 size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces);
+size_t pd_tables_bytes(int nfiles, int npieces);  // the tables' part alone: the least workspace a call is taken with
 hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                              hipStream_t stream);

@@ -39,7 +39,6 @@ __constant__ uint32_t jpeg_dc_codes[2][12] = { { JPEG_DC0_CODES }, { JPEG_DC1_CO
 __constant__ uint32_t jpeg_ac_codes[2][256] = { { JPEG_AC0_CODES }, { JPEG_AC1_CODES } };
 
 // ---- layout, tables and the file header (host) ----
-static size_t jpeg_round16(size_t v) { return (v + 15) & ~(size_t)15; }
 JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interval)
 {
     JpegLayout l;
@@ -54,9 +53,11 @@ JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interva
     l.blocks = l.mcus * (size_t)l.bpm;
     l.intervals = (l.mcus + (size_t)l.ri - 1) / (size_t)l.ri;
     l.file_header = C == 3 ? 629 : 334;
-    l.sizes_off = l.blocks * 128;
-    l.fits_off = l.sizes_off + jpeg_round16(l.intervals * 4);
-    l.per_picture = l.fits_off + 16;
+    GsrCarver c(nullptr);  // offsets only: the kernels add them to the start of the picture's part
+    c.skip(l.blocks * 128, 16);
+    l.sizes_off = c.bytes(); c.skip(l.intervals * 4, 16);
+    l.fits_off = c.bytes(); c.skip(16, 16);
+    l.per_picture = c.total();
     l.capacity = l.file_header + l.blocks * JPEG_BLOCK_BYTES + l.mcus * 3 + 2;
     return l;
 }

@@ -264,20 +264,19 @@ struct GskWorkspace {
 static GskWorkspace gsk_carve(void* base, int P)
 {
     GskWorkspace w;
-    char* b = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t p = (size_t)(P > 0 ? P : 1);
-    w.codes = (uint32_t*)(b + off); off += gsr_align(p * 4);
-    w.ids_sorted = (uint32_t*)(b + off); off += gsr_align(p * 4);
-    w.seg_keys = (unsigned long long*)(b + off); off += gsr_align(p * 8);
-    w.ranges = (uint2*)(b + off); off += gsr_align((size_t)GSK_BUCKETS * sizeof(uint2));
-    w.bucket_count = (uint32_t*)(b + off); off += gsr_align((size_t)GSK_BUCKETS * 4);
-    w.cursor = (uint32_t*)(b + off); off += gsr_align((size_t)GSK_BUCKETS * 4);
-    w.sp = (float4*)(b + off); off += gsr_align(p * 16);
-    w.boxes = (GskBox*)(b + off); off += gsr_align(((p + GSK_BOX - 1) / GSK_BOX) * sizeof(GskBox));
-    w.sboxes = (GskBox*)(b + off); off += gsr_align(((p + GSK_BOX * GSK_BOX - 1) / (GSK_BOX * GSK_BOX)) * sizeof(GskBox));
-    w.part = (float*)(b + off); off += gsr_align(GSK_MINMAX_BLOCKS * 6 * 4);
-    w.bytes = off;
+    w.codes = c.take<uint32_t>(p);
+    w.ids_sorted = c.take<uint32_t>(p);
+    w.seg_keys = c.take<unsigned long long>(p);
+    w.ranges = c.take<uint2>(GSK_BUCKETS);
+    w.bucket_count = c.take<uint32_t>(GSK_BUCKETS);
+    w.cursor = c.take<uint32_t>(GSK_BUCKETS);
+    w.sp = c.take<float4>(p);
+    w.boxes = c.take<GskBox>((p + GSK_BOX - 1) / GSK_BOX);
+    w.sboxes = c.take<GskBox>((p + GSK_BOX * GSK_BOX - 1) / (GSK_BOX * GSK_BOX));
+    w.part = c.take<float>(GSK_MINMAX_BLOCKS * 6);
+    w.bytes = c.total();
     return w;
 }
 

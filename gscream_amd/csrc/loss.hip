@@ -261,15 +261,14 @@ struct GslWorkspace {
 static GslWorkspace gsl_carve(void* base, int C, int H, int W)
 {
     GslWorkspace w;
-    char* b = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t n = (size_t)(C > 0 ? C : 1) * (H > 0 ? H : 1) * (W > 0 ? W : 1);
     w.gx = (W + GSL_TW - 1) / GSL_TW; w.gy = (H + GSL_TH - 1) / GSL_TH;
-    w.d_mu1 = (float*)(b + off); off += gsr_align(n * 4);
-    w.d_e11 = (float*)(b + off); off += gsr_align(n * 4);
-    w.d_e12 = (float*)(b + off); off += gsr_align(n * 4);
-    w.partial = (GslPartial*)(b + off); off += gsr_align((size_t)(w.gx > 0 ? w.gx : 1) * (w.gy > 0 ? w.gy : 1) * (C > 0 ? C : 1) * sizeof(GslPartial));
-    w.bytes = off;
+    w.d_mu1 = c.take<float>(n);
+    w.d_e11 = c.take<float>(n);
+    w.d_e12 = c.take<float>(n);
+    w.partial = c.take<GslPartial>((size_t)(w.gx > 0 ? w.gx : 1) * (w.gy > 0 ? w.gy : 1) * (C > 0 ? C : 1));
+    w.bytes = c.total();
     return w;
 }
 

@@ -301,7 +301,6 @@ static const int lp_widths[13][2] = {{3, 64}, {64, 64}, {64, 128}, {128, 128}, {
 static const int lp_group_end[5] = {1, 3, 6, 9, 12};  // the layer whose ReLU output is tap l
 static const int lp_tap_channels[5] = {64, 128, 256, 512, 512};
 
-static size_t lp_align(size_t n) { return (n + 511) / 512 * 512; }
 static size_t lp_packed_floats(int Cin, int Cout) { return (size_t)(Cout / LPC_NB) * (size_t)((Cin + LPC_KC - 1) / LPC_KC) * LPC_WCHUNK; }
 static int lp_blocks(long long hw) { return (int)((hw + LP_THREADS - 1) / LP_THREADS); }
 
@@ -317,45 +316,42 @@ hipError_t lpips_launch_conv(int N, int Cin, int Cout, int H, int W, const float
 // the carve of the workspace: two activation buffers of 2B*64*H*W floats (the largest stage), the five maps, the head partials, the
 // spatial partials; every piece on a 512-byte boundary
 struct lp_carve {
-    size_t buf, map[5], head[5], spatial, total;
+    float *buf[2], *map[5];
+    double *head[5], *spatial;
+    size_t total;
     int h[5], w[5], blocks[5], sblocks;
 };
 
-static lp_carve lp_plan(int B, int H, int W)
+static lp_carve lp_plan(void* base, int B, int H, int W)
 {
-    lp_carve c;
-    size_t at = 0;
-    c.buf = lp_align((size_t)2 * (size_t)B * 64 * (size_t)H * (size_t)W * sizeof(float));
-    at = 2 * c.buf;
+    lp_carve p;
+    GsrCarver c(base);
+    for (int k = 0; k < 2; k++) p.buf[k] = c.take<float>((size_t)2 * (size_t)B * 64 * (size_t)H * (size_t)W, 512);
     int h = H, w = W;
     for (int l = 0; l < 5; l++) {
-        c.h[l] = h;
-        c.w[l] = w;
-        c.blocks[l] = lp_blocks((long long)h * w);
-        c.map[l] = at;
-        at += lp_align((size_t)B * (size_t)h * (size_t)w * sizeof(float));
-        c.head[l] = at;
-        at += lp_align((size_t)B * (size_t)c.blocks[l] * sizeof(double));
+        p.h[l] = h;
+        p.w[l] = w;
+        p.blocks[l] = lp_blocks((long long)h * w);
+        p.map[l] = c.take<float>((size_t)B * (size_t)h * (size_t)w, 512);
+        p.head[l] = c.take<double>((size_t)B * (size_t)p.blocks[l], 512);
         h /= 2;
         w /= 2;
     }
-    c.sblocks = lp_blocks((long long)H * W);
-    c.spatial = at;
-    at += lp_align((size_t)B * (size_t)c.sblocks * 2 * sizeof(double));
-    c.total = at;
-    return c;
+    p.sblocks = lp_blocks((long long)H * W);
+    p.spatial = c.take<double>((size_t)B * (size_t)p.sblocks * 2, 512);
+    p.total = c.total();
+    return p;
 }
 
-size_t lpips_workspace_bytes(int B, int H, int W) { return lp_plan(B, H, W).total; }
+size_t lpips_workspace_bytes(int B, int H, int W) { return lp_plan(nullptr, B, H, W).total; }
 
 hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
                         const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
                         float* out_layers, float* out_masked, float* out_spatial, hipStream_t stream)
 {
-    const lp_carve c = lp_plan(B, H, W);
-    char* base = (char*)workspace;
-    float* cur = (float*)base;             // holds the newest activations
-    float* other = (float*)(base + c.buf);
+    const lp_carve c = lp_plan(workspace, B, H, W);
+    float* cur = c.buf[0];  // holds the newest activations
+    float* other = c.buf[1];
     hipError_t e;
     lp_levels lv;
     lp_finish_args fa;
@@ -387,8 +383,8 @@ hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1,
             wp += lp_packed_floats(Cin, Cout);
             bp += Cout;
         }
-        float* map = (float*)(base + c.map[l]);
-        double* part = (double*)(base + c.head[l]);
+        float* map = c.map[l];
+        double* part = c.head[l];
         const long long hw = (long long)h * w;
         hipLaunchKernelGGL(lpips_head_kernel, dim3((uint32_t)c.blocks[l], (uint32_t)B), dim3(LP_THREADS), 0, stream, B, lp_tap_channels[l], hw,
                            (const float*)cur, lp, map, part);
@@ -401,7 +397,7 @@ hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1,
         fa.blocks[l] = c.blocks[l];
         fa.pixels[l] = (double)hw;
     }
-    double* sp = (double*)(base + c.spatial);
+    double* sp = c.spatial;
     hipLaunchKernelGGL(lpips_spatial_kernel, dim3((uint32_t)c.sblocks, (uint32_t)B), dim3(LP_THREADS), 0, stream, H, W, lv, mask, mask_stride_b,
                        out_spatial, sp);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -42,7 +42,6 @@
 #define MET_SH (MET_TH + 2 * MET_R)   // 20 staged rows
 static_assert(MET_TW == 32, "a 32-lane half is one tile row: 32 consecutive doubles cover the 64 banks once");
 static_assert(MET_THREADS == MET_TW * MET_TH / 2, "two pixels per thread");
-static_assert(METRICS_TILE_W == MET_TW && METRICS_TILE_H == MET_TH, "gsr_common.h sizes the workspace by the same tile");
 
 __device__ __forceinline__ float met_transform(float x, int flags)
 {
@@ -181,17 +180,28 @@ __global__ void __launch_bounds__(MET_THREADS) metrics_finish_kernel(int per_ima
     }
 }
 
+// workspace[(b*C + c)*tiles + tile]: the eight sums of each tile, nothing between them
+struct MetWork { double* partials; int tiles_x, tiles; size_t bytes; };
+static MetWork met_carve(void* base, int B, int C, int H, int W)
+{
+    GsrCarver c(base);
+    const int tiles_x = (W + MET_TW - 1) / MET_TW, tiles_y = (H + MET_TH - 1) / MET_TH;  // tiles_x * tiles_y < 2^31 / 3: C*H*W < 2^31
+    double* partials = c.take<double>((size_t)B * (size_t)C * (size_t)tiles_x * (size_t)tiles_y * 8, sizeof(double));
+    return { partials, tiles_x, tiles_x * tiles_y, c.total() };
+}
+size_t metrics_workspace_bytes(int B, int C, int H, int W) { return met_carve(nullptr, B, C, H, W).bytes; }
+
 hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
                           long long mask_stride_c, int flags, const double taps[3], void* workspace, double* sums, float* metrics,
                           hipStream_t stream)
 {
-    const int tiles_x = (W + MET_TW - 1) / MET_TW, tiles_y = (H + MET_TH - 1) / MET_TH;  // tiles_x * tiles_y < 2^31 / 3: C*H*W < 2^31
-    const int tiles = tiles_x * tiles_y;
+    const MetWork w = met_carve(workspace, B, C, H, W);
+    const int tiles_x = w.tiles_x, tiles = w.tiles;
     met_taps t = {taps[0], taps[1], taps[2]};
     hipLaunchKernelGGL(metrics_tile_kernel, dim3((uint32_t)tiles, (uint32_t)(B * C)), dim3(MET_THREADS), 0, stream, H, W, C, tiles_x, pred, gt,
-                       mask, mask_stride_b, mask_stride_c, flags, t, (double*)workspace);
+                       mask, mask_stride_b, mask_stride_c, flags, t, w.partials);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(metrics_finish_kernel, dim3((uint32_t)B), dim3(MET_THREADS), 0, stream, C * tiles, (const double*)workspace, sums, metrics);
+    hipLaunchKernelGGL(metrics_finish_kernel, dim3((uint32_t)B), dim3(MET_THREADS), 0, stream, C * tiles, (const double*)w.partials, sums, metrics);
     return hipGetLastError();
 }

@@ -37,17 +37,18 @@ static_assert(PNG_PER == 32, "a thread's run heads are one 32-bit mask, and at m
 static_assert(PNG_SLOT_BYTES >= PNG_CHUNK + 2 + 5 + 5 + 4 && PNG_SLOT_BYTES % 16 == 0, "zlib header, stored header, marker, one dword of slack");
 
 // ---- layout of the workspace (per picture; every part a multiple of 16 bytes) ----
-static size_t png_round16(size_t v) { return (v + 15) & ~(size_t)15; }
 PngLayout png_layout(int H, int W, int C)
 {
     PngLayout l;
     l.row_bytes = 1 + (size_t)W * (size_t)C;
     l.stream_bytes = (size_t)H * l.row_bytes;
     l.chunks = (l.stream_bytes + PNG_CHUNK - 1) / PNG_CHUNK;
-    l.adler_off = png_round16(l.stream_bytes);
-    l.sizes_off = l.adler_off + png_round16((size_t)H * 8);
-    l.slots_off = l.sizes_off + png_round16(l.chunks * 4);
-    l.per_picture = l.slots_off + l.chunks * PNG_SLOT_BYTES;
+    GsrCarver c(nullptr);  // offsets only: the kernels add them to the start of the picture's part
+    c.skip(l.stream_bytes, 16);
+    l.adler_off = c.bytes(); c.skip((size_t)H * 8, 16);
+    l.sizes_off = c.bytes(); c.skip(l.chunks * 4, 16);
+    l.slots_off = c.bytes(); c.skip(l.chunks * PNG_SLOT_BYTES, 16);
+    l.per_picture = c.total();
     // signature, IHDR, per chunk {length, type, CRC, stored header, marker}, the stream, zlib header, Adler-32, IEND
     l.capacity = 8 + 25 + l.chunks * (12 + 5 + 5) + l.stream_bytes + 2 + 4 + 12;
     return l;

@@ -40,17 +40,34 @@ static_assert(PNGI_TABLE == GSR_PNG_TABLE && PNGI_CRC == GSR_PNG_CRC && PNGI_TRU
 #define PD_CRC_THREADS 256
 #define PD_SEG (GSR_PNG_PIECE_IDAT | GSR_PNG_PIECE_START)
 
-static size_t pd_round16(size_t v) { return (v + 15) & ~(size_t)15; }
-size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces)
-{
-    return pd_round16(stream_bytes) + pd_round16((size_t)npieces * 12) + pd_round16((size_t)nfiles * 4);
-}
-
 struct PdWorkspace {
     uint8_t* streams;
     unsigned long long stream_area;
     uint32_t *seg_size, *seg_flag, *seg_off, *trailer;
 };
+
+// The streams' area of `stream_bytes` (rounded up to 16), then the tables: per piece {size, flag, offset} as three arrays in one
+// piece, per file the trailer's Adler-32.  The launcher puts the tables at the END of what the caller gave: its stream area is
+// whatever lies in front of them.
+struct PdCarve {
+    PdWorkspace ws;
+    size_t bytes;
+};
+static PdCarve pd_carve(void* base, size_t stream_bytes, int nfiles, int npieces)
+{
+    PdCarve r{};
+    GsrCarver c(base);
+    r.ws.streams = c.take<uint8_t>(stream_bytes, 16);
+    r.ws.stream_area = c.bytes();
+    r.ws.seg_size = c.take<uint32_t>((size_t)npieces * 3, 16);
+    r.ws.seg_flag = r.ws.seg_size ? r.ws.seg_size + npieces : nullptr;
+    r.ws.seg_off = r.ws.seg_size ? r.ws.seg_flag + npieces : nullptr;
+    r.ws.trailer = c.take<uint32_t>((size_t)nfiles, 16);
+    r.bytes = c.total();
+    return r;
+}
+size_t pd_tables_bytes(int nfiles, int npieces) { return pd_carve(nullptr, 0, nfiles, npieces).bytes; }
+size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces) { return pd_carve(nullptr, stream_bytes, nfiles, npieces).bytes; }
 
 struct PdTeam {
     int lane, lanes;
@@ -387,15 +404,9 @@ hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_
                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                              hipStream_t stream)
 {
-    const size_t tables = pd_round16((size_t)npieces * 12) + pd_round16((size_t)nfiles * 4);
+    const size_t tables = pd_tables_bytes(nfiles, npieces);
     if (workspace_bytes < tables) return hipErrorInvalidValue;
-    PdWorkspace ws;
-    ws.streams = (uint8_t*)workspace;
-    ws.stream_area = (workspace_bytes - tables) & ~(size_t)15;
-    ws.seg_size = (uint32_t*)(ws.streams + ws.stream_area);
-    ws.seg_flag = ws.seg_size + npieces;
-    ws.seg_off = ws.seg_flag + npieces;
-    ws.trailer = (uint32_t*)(ws.streams + ws.stream_area + pd_round16((size_t)npieces * 12));
+    const PdWorkspace ws = pd_carve(workspace, (workspace_bytes - tables) & ~(size_t)15, nfiles, npieces).ws;
     static thread_local uint64_t done_mask = 0;  // the ring and the tables are beyond 64 KiB of LDS: a one-time opt-in per device
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);

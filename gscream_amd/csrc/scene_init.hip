@@ -199,42 +199,32 @@ struct GsiSortWork {
     uint32_t* tsum;   // [tiles of bhist + 1]
     gsi_u64* tmp;     // [N]
     int nb, nt;
+    size_t bytes;
 };
 
-static GsiSortWork gsi_sort_carve(void* base, int N, size_t* bytes)
+static GsiSortWork gsi_sort_carve(void* base, int N)
 {
     GsiSortWork w{};
-    char* p = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t n = (size_t)(N > 0 ? N : 1);
     w.nb = gsi_blocks((long long)n, GSR_SORT_BLOCK_KEYS);
     w.nt = gsi_blocks(256LL * w.nb, GSI_SCAN_TILE);
-    w.ctl = (uint32_t*)(p + off);
-    off += gsr_align((size_t)GSI_CTL_WORDS * 4);
-    w.ghist = (uint32_t*)(p + off);
-    off += gsr_align((size_t)GSI_PASSES * 256 * 4);
-    w.bhist = (uint32_t*)(p + off);
-    off += gsr_align((size_t)256 * w.nb * 4);
-    w.tsum = (uint32_t*)(p + off);
-    off += gsr_align(((size_t)w.nt + 1) * 4);
-    w.tmp = (gsi_u64*)(p + off);
-    off += gsr_align(n * 8);
-    if (bytes) *bytes = off;
+    w.ctl = c.take<uint32_t>(GSI_CTL_WORDS);
+    w.ghist = c.take<uint32_t>((size_t)GSI_PASSES * 256);
+    w.bhist = c.take<uint32_t>((size_t)256 * w.nb);
+    w.tsum = c.take<uint32_t>((size_t)w.nt + 1);
+    w.tmp = c.take<gsi_u64>(n);
+    w.bytes = c.total();
     return w;
 }
 
-size_t gsi_sort_workspace_bytes(int N)
-{
-    size_t b = 0;
-    (void)gsi_sort_carve(nullptr, N, &b);
-    return b;
-}
+size_t gsi_sort_workspace_bytes(int N) { return gsi_sort_carve(nullptr, N).bytes; }
 
 hipError_t gsi_sort_launch(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, hipStream_t stream)
 {
     if (N == 0) return hipSuccess;
     hipError_t e;
-    const GsiSortWork w = gsi_sort_carve(workspace, N, nullptr);
+    const GsiSortWork w = gsi_sort_carve(workspace, N);
     const gsi_u64* in = (const gsi_u64*)keys_in;
     gsi_u64* out = (gsi_u64*)keys_out;
     if ((e = hipMemsetAsync(w.ghist, 0, (size_t)GSI_PASSES * 256 * 4, stream)) != hipSuccess) return e;
@@ -423,38 +413,29 @@ struct GsiVoxWork {
     gsi_u64* keys;   // [N]
     uint32_t* bsum;  // [blocks(N) + 1] heads per workgroup, scanned in place
     void* sort;      // gsi_sort_workspace_bytes(N)
+    size_t bytes;
 };
 
-static GsiVoxWork gsi_vox_carve(void* base, int N, size_t* bytes)
+static GsiVoxWork gsi_vox_carve(void* base, int N)
 {
     GsiVoxWork w{};
-    char* p = (char*)base;
-    size_t off = 0;
+    GsrCarver c(base);
     const size_t n = (size_t)(N > 0 ? N : 1);
-    w.head = (int32_t*)(p + off);
-    off += gsr_align((size_t)GSI_HEAD_WORDS * 4);
-    w.keys = (gsi_u64*)(p + off);
-    off += gsr_align(n * 8);
-    w.bsum = (uint32_t*)(p + off);
-    off += gsr_align(((size_t)gsi_blocks((long long)n, GSI_THREADS) + 1) * 4);
-    w.sort = (void*)(p + off);
-    off += gsi_sort_workspace_bytes(N);
-    if (bytes) *bytes = off;
+    w.head = c.take<int32_t>(GSI_HEAD_WORDS);
+    w.keys = c.take<gsi_u64>(n);
+    w.bsum = c.take<uint32_t>((size_t)gsi_blocks((long long)n, GSI_THREADS) + 1);
+    w.sort = c.take<uint8_t>(gsi_sort_workspace_bytes(N));
+    w.bytes = c.total();
     return w;
 }
 
-size_t gsi_voxelize_workspace_bytes(int N)
-{
-    size_t b = 0;
-    (void)gsi_vox_carve(nullptr, N, &b);
-    return b;
-}
+size_t gsi_voxelize_workspace_bytes(int N) { return gsi_vox_carve(nullptr, N).bytes; }
 
 template <typename T>
 static hipError_t gsi_voxelize_typed(int N, const T* pts, double v_host, const float* v_dev, void* workspace, T* out, int32_t* info,
                                      hipStream_t stream)
 {
-    const GsiVoxWork w = gsi_vox_carve(workspace, N, nullptr);
+    const GsiVoxWork w = gsi_vox_carve(workspace, N);
     const int nb = gsi_blocks(N, GSI_THREADS);
     hipLaunchKernelGGL(gsi_vox_init_kernel, dim3(1), dim3(64), 0, stream, w.head);
     hipLaunchKernelGGL(gsi_vox_range_kernel<T>, dim3(nb), dim3(GSI_THREADS), 0, stream, N, pts, v_host, v_dev, w.head);
@@ -529,15 +510,23 @@ __global__ void __launch_bounds__(256) gsi_kth_pick_kernel(int level, int k_arg,
     }
 }
 
+struct GsiKthWork { uint32_t* ws; size_t bytes; };  // [GSI_KTH_WORDS], whatever N
+static GsiKthWork gsi_kth_carve(void* base)
+{
+    GsrCarver c(base);
+    uint32_t* ws = c.take<uint32_t>(GSI_KTH_WORDS);
+    return { ws, c.total() };
+}
+
 size_t gsi_kth_workspace_bytes(int N)
 {
     (void)N;
-    return gsr_align((size_t)GSI_KTH_WORDS * 4);
+    return gsi_kth_carve(nullptr).bytes;
 }
 
 hipError_t gsi_kth_launch(int N, int k, const float* values, void* workspace, float* out, hipStream_t stream)
 {
-    uint32_t* ws = (uint32_t*)workspace;
+    uint32_t* ws = gsi_kth_carve(workspace).ws;
     hipError_t e;
     if ((e = hipMemsetAsync(ws, 0, (size_t)GSI_KTH_WORDS * 4, stream)) != hipSuccess) return e;
     const int nb = gsi_blocks(N, GSI_KTH_TILE);
