@@ -11,7 +11,7 @@ patch()      a context manager (pytest's monkeypatch) that makes the allocation 
              zeros, ones, full, their *_like and Tensor.new_* forms, and the copies .to / .cuda / .clone / .contiguous / .float make --
              return views of arena bodies for the arena's device.  empty() leaves the poison in the body; zeros / ones / full fill the
              body only.  Other devices and pinned memory pass through.  Copies are adopted only where autograd does not track them.
-header_table parses include/gsraster.h (comments stripped) into {function: [(type, name, is_pointer, is_const)]}.
+header_table the parameter lists gscream_amd/_abi.py reads from include/gsraster.h: {function: [(type, name, is_pointer, is_const)]}.
 LibProxy     stands in for _native._lib (both _native.load() and _native.run() go through it).  On every call each non-NULL pointer
              argument declared non-const must lie inside an arena body ("unguarded writable buffer: function, parameter"), and each
              const pointer argument that lies in a body is copied before the call and compared bit for bit after it.  The pointers
@@ -29,14 +29,13 @@ an out-of-bounds READ that changes no output, or a write beyond the 64 KiB guard
 import bisect
 import contextlib
 import ctypes
-import os
-import re
 
 import torch
 
+from gscream_amd import _abi
+
 ALIGN = 512
 GUARD = 64 * 1024
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gsraster.h")
 
 #: (function, parameter) -> why it is host memory.  ("*", "stream") stands for the `void* stream` every launching entry point ends in.
 HOST_PARAMS = {
@@ -78,26 +77,9 @@ class GuardError(AssertionError):
 
 # ---- the header table ----------------------------------------------------------------------------------------------------------
 
-def header_table(path=HEADER):
-    """{function: [(type, name, is_pointer, is_const)]} of every function include/gsraster.h declares."""
-    with open(path) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
-    text = re.sub(r"typedef\s+(struct|enum)[^{;]*\{.*?\}[^;]*;", " ", text, flags=re.S)
-    text = re.sub(r"\benum\s*\{.*?\}\s*;", " ", text, flags=re.S)
-    table = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(gsr_\w+)\s*\(([^()]*)\)\s*;", text):
-        params = []
-        body = " ".join(m.group(3).split())
-        if body and body != "void":
-            for p in body.split(","):
-                pm = re.match(r"^(.*?)(\w+)$", p.strip())
-                ctype, name = pm.group(1).strip().replace(" *", "*"), pm.group(2)
-                params.append((ctype, name, "*" in ctype, ctype.startswith("const ")))
-        table[m.group(2)] = params
-    return table
+def header_table():
+    """{function: [(type, name, is_pointer, is_const)]} of every function include/gsraster.h declares: the package's own reading."""
+    return {name: params for name, (_, params) in _abi.header().functions.items()}
 
 
 # ---- the arena -----------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@ tests/golden/ref_adjust_anchor.npz was recorded by running the reference's own G
 step it calls replaced by the restatement tests/test_anchor_grow.py checks against its own fixture (the HIP growing step needs a
 device); that makes the torch path the ground truth the GPU tests (tests/test_gpu_anchor_adjust.py) compare the kernels with."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -190,23 +189,19 @@ def test_prune_anchor_torch_path_equals_a_row_loop(state):
 
 def test_new_symbols_in_header_binding_and_library(native_lib):
     import ctypes
-    from gscream_amd import _native
-    text = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    from gscream_amd import _abi, _native
+    hdr = _abi.header()
     for s in NEW_SYMBOLS:
-        assert re.search(r"\b" + s + r"\s*\(", hdr), s
+        assert s in hdr.functions, s
         assert s in _native.EXPORTED_SYMBOLS, s
         assert hasattr(native_lib, s), s
     assert native_lib.gsr_anchor_adjust_workspace_bytes(1000) > 0
-    assert int(re.search(r"#define GSR_ADJUST_MAX_COPIES (\d+)", hdr).group(1)) == _native.ADJUST_MAX_COPIES == 32
-    body = re.search(r"typedef struct gsr_adjust_copy \{(.*?)\}", hdr, flags=re.S).group(1)
-    assert [f.split()[-1] for f in body.split(";") if f.strip()] == [n for n, _t in _native.AdjustCopy._fields_]
+    assert hdr.constants["GSR_ADJUST_MAX_COPIES"] == _native.ADJUST_MAX_COPIES == 32
+    assert [f for _, f, _ in hdr.structs["gsr_adjust_copy"]] == [n for n, _t in _native.AdjustCopy._fields_]
     assert ctypes.sizeof(_native.AdjustCopy) == 24
-    modes = re.search(r"enum \{ (GSR_ADJUST_COPY.*?) \}", hdr).group(1)
-    assert [m.split(" = ") for m in modes.split(", ")] == [["GSR_ADJUST_COPY", "0"], ["GSR_ADJUST_CLAMP_TAIL", "1"],
-                                                           ["GSR_ADJUST_OFFSET_STAT", "2"], ["GSR_ADJUST_ANCHOR_STAT", "3"]]
+    assert [hdr.constants["GSR_ADJUST_" + m] for m in ("COPY", "CLAMP_TAIL", "OFFSET_STAT", "ANCHOR_STAT")] == [0, 1, 2, 3]
     assert (_native.ADJUST_COPY, _native.ADJUST_CLAMP_TAIL, _native.ADJUST_OFFSET_STAT, _native.ADJUST_ANCHOR_STAT) == (0, 1, 2, 3)
-    assert re.search(r"#define GSR_ABI_VERSION 8\b", text)  # additions only
+    assert hdr.constants["GSR_ABI_VERSION"] == 8  # additions only
 
 
 def test_native_argument_checks(native_lib):

@@ -3,7 +3,6 @@ the stored runs of the reference's compute_scale_and_shift, the torch path again
 agreement of header, binding and library, and everything the two C calls and the Python layer reject before anything is launched."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -224,19 +223,18 @@ def test_the_colour_tables_are_what_matplotlib_gives():
 
 # ---- header, binding, library ----
 def test_header_binding_and_library_agree(native_lib):
-    from gscream_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    assert re.search(r"#define\s+GSR_ABI_VERSION\s+8\b", hdr) and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
-    assert re.search(r"#define\s+GSR_FRAME_MAX_PANELS\s+8\b", hdr) and _native.FRAME_MAX_PANELS == 8 == Fr.MAX_PANELS
+    from gscream_amd import _abi, _native
+    hdr = _abi.header()
+    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_FRAME_MAX_PANELS"] == 8 and _native.FRAME_MAX_PANELS == 8 == Fr.MAX_PANELS
     for k, name in enumerate(("QUANT", "QUANT_CLAMP", "ABSDIFF", "NORMAL", "CMAP_CV", "CMAP_MPL_ALIGNED", "CMAP_MPL")):
-        assert re.search(rf"#define\s+GSR_FRAME_{name}\s+{k}\b", hdr) and getattr(_native, f"FRAME_{name}") == k == getattr(Fr, name) == getattr(O, name)
-    assert re.search(r"\bsize_t\s+gsr_frame_stats_workspace_bytes\s*\(", hdr) and re.search(r"\bint\s+gsr_frame_stats\s*\(", hdr)
-    assert re.search(r"\bint\s+gsr_frame_compose\s*\(", hdr)
+        assert hdr.constants[f"GSR_FRAME_{name}"] == k and getattr(_native, f"FRAME_{name}") == k == getattr(Fr, name) == getattr(O, name)
+    assert hdr.functions["gsr_frame_stats_workspace_bytes"][0] == "size_t" and hdr.functions["gsr_frame_stats"][0] == "int"
+    assert hdr.functions["gsr_frame_compose"][0] == "int"
     for name in ("gsr_frame_stats_workspace_bytes", "gsr_frame_stats", "gsr_frame_compose"):
         assert name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
     assert len(native_lib.gsr_frame_stats.argtypes) == 10 and len(native_lib.gsr_frame_compose.argtypes) == 9
-    struct = re.search(r"typedef struct \{([^}]*)\} gsr_frame_panel;", hdr).group(1)
-    declared = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", struct))
+    declared = [f for _, f, _ in hdr.structs["gsr_frame_panel"]]
     assert declared == [f[0] for f in _native.FramePanel._fields_] and ctypes.sizeof(_native.FramePanel) == 72
     for lib in ("libgsraster_precise.so", "libgsraster_replayall.so"):  # the two test builds link the same objects
         path = os.path.join(os.path.dirname(_native.LIB_PATH), lib)

@@ -13,17 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol(native_lib):
-    from gscream_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_native.EXPORTED_SYMBOLS), declared ^ set(_native.EXPORTED_SYMBOLS)
+    from gscream_amd import _abi, _native
+    declared = set(_abi.header().functions)
+    assert len(declared) == 80 and declared == set(_native.EXPORTED_SYMBOLS), declared ^ set(_native.EXPORTED_SYMBOLS)
     for sym in declared:
         assert hasattr(native_lib, sym), sym
     assert native_lib.gsr_version().startswith(b"gsraster")
     # the integer ABI version of the header == the library's == the binding's (a stale .so fails at load time, not in a kernel)
-    m = re.search(r"#define\s+GSR_ABI_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "gsraster.h")).read())
-    assert m and int(m.group(1)) == native_lib.gsr_abi_version() == _native.ABI_VERSION
+    assert _abi.header().constants["GSR_ABI_VERSION"] == native_lib.gsr_abi_version() == _native.ABI_VERSION
 
 
 def test_tuning_struct_layout_and_the_inference_twin():

@@ -199,12 +199,12 @@ def test_evaluate_views_keys(model):
 
 
 def test_header_binding_and_library_agree(native_lib):
-    from gscream_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    assert re.search(r"#define\s+GSR_LPIPS_NORMALIZE\s+1\b", hdr) and re.search(r"#define\s+GSR_LPIPS_SCALING\s+2\b", hdr)
+    from gscream_amd import _abi, _native
+    hdr = _abi.header()
+    assert hdr.constants["GSR_LPIPS_NORMALIZE"] == 1 and hdr.constants["GSR_LPIPS_SCALING"] == 2
     assert (LP.NORMALIZE, LP.SCALING) == (1, 2)
-    assert re.search(r"\bsize_t\s+gsr_lpips_workspace_bytes\s*\(", hdr) and re.search(r"\bint\s+gsr_lpips\s*\(", hdr)
-    assert re.search(r"\bint\s+gsr_conv3x3_relu\s*\(", hdr)
+    assert hdr.functions["gsr_lpips_workspace_bytes"][0] == "size_t" and hdr.functions["gsr_lpips"][0] == "int"
+    assert hdr.functions["gsr_conv3x3_relu"][0] == "int"
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import arena_helpers as A
     table = A.header_table()
@@ -216,7 +216,7 @@ def test_header_binding_and_library_agree(native_lib):
     writable = [p[1] for p in table["gsr_lpips"] if p[2] and not p[3]]
     assert writable == ["workspace", "out_plain", "out_layers", "out_masked", "out_spatial", "stream"]
     assert [p[1] for p in table["gsr_conv3x3_relu"] if p[2] and not p[3]] == ["out", "stream"]
-    assert re.search(r"#define\s+GSR_ABI_VERSION\s+8\b", hdr), "new exports do not change the ABI version"
+    assert hdr.constants["GSR_ABI_VERSION"] == 8, "new exports do not change the ABI version"
 
 
 def test_argument_checks_without_a_gpu(native_lib):

@@ -2,7 +2,6 @@
 module's torch path, the reference's return layout, the point map, and the argument checks of gsr_depth_points / gsr_point_normals.
 Bounds: tests/normals_helpers.py."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -167,11 +166,11 @@ def test_other_sizes_and_bad_arguments_on_the_torch_path():
 
 
 def test_header_binding_and_library_have_the_two_calls(native_lib):
-    from gscream_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    assert re.search(r"#define\s+GSR_ABI_VERSION\s+8\b", hdr) and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    from gscream_amd import _abi, _native
+    hdr = _abi.header()
+    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
     for name in ("gsr_depth_points", "gsr_point_normals"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
+        assert hdr.functions[name][0] == "int" and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
     assert len(native_lib.gsr_depth_points.argtypes) == 7 and len(native_lib.gsr_point_normals.argtypes) == 8
     for lib in ("libgsraster_precise.so", "libgsraster_replayall.so"):  # the two test builds link the same objects
         import ctypes

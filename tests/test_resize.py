@@ -208,20 +208,21 @@ def test_resize_pil_image_routes_by_mode(monkeypatch):
 
 
 def test_abi_entries(native_lib):
-    from gscream_amd import _native
-    hdr = open(os.path.join(ROOT, "include", "gsraster.h")).read()
-    assert re.search(r"#define\s+GSR_ABI_VERSION\s+8\b", hdr) and native_lib.gsr_abi_version() == 8 and _native.ABI_VERSION == 8
+    from gscream_amd import _abi, _native
+    hdr = _abi.header()
+    assert hdr.constants["GSR_ABI_VERSION"] == 8 and native_lib.gsr_abi_version() == 8 and _native.ABI_VERSION == 8
     table = A.header_table()
     names = ("gsr_resize_u8", "gsr_resize_f32", "gsr_resize_nearest_u8", "gsr_resize_nearest_f32")
     for name in names:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
+        assert hdr.functions[name][0] == "int" and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
         params = table[name]
         assert params[-1] == ("void*", "stream", True, False)
         assert len(params) == len(getattr(native_lib, name).argtypes)
         # device pointers only: every pointer parameter but the stream is device memory, so none is on the host-parameter list
         assert not [p for p in params if (name, p[1]) in A.HOST_PARAMS]
         assert [p[1] for p in params if p[2] and not p[3]] == ["out", "stream"]
-    assert re.search(r"#define\s+GSR_RESIZE_PRECISION_BITS\s+22\b", hdr)
+    assert hdr.constants["GSR_RESIZE_PRECISION_BITS"] == 22
+    assert [hdr.constants["GSR_RESIZE_" + n] for n in ("HORIZONTAL", "VERTICAL", "U8", "DIV255", "GT0")] == [0, 1, 0, 1, 2]
     assert (_native.RESIZE_HORIZONTAL, _native.RESIZE_VERTICAL, _native.RESIZE_U8, _native.RESIZE_DIV255, _native.RESIZE_GT0) == (0, 1, 0, 1, 2)
     buf = (_native.ctypes.c_uint8 * 64)()
     assert native_lib.gsr_resize_u8(buf, 64, 8, 1, 8, 8, 5, 0, 4, buf, buf, 3, buf, 32, 4, 0, None) == -1 and b"C=5" in native_lib.gsr_last_error()
