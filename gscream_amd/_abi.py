@@ -28,8 +28,9 @@ def _declarator(text):
     return re.sub(r"\s*\*", "*", m.group(1).strip()), m.group(2), m.group(3)
 
 
-def parse(text):
-    """The text of a header in gsraster.h's style -> Abi(functions, constants, structs)."""
+def parse(text, scope=None):
+    """The text of a header in gsraster.h's style -> Abi(functions, constants, structs).  scope: constants of another header that an
+    array length here may name (an extension header read with the main header's in scope); they are not repeated in the result."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     constants = {m.group(1): int(m.group(2), 0)
@@ -54,7 +55,7 @@ def parse(text):
             first, *more = decl.split(",")
             ctype, name, length = _declarator(first)
             for name, length in [(name, length)] + [_declarator(ctype + " " + d)[1:] for d in more]:
-                fields.append((ctype, name, None if length is None else int(length) if length.isdigit() else constants[length]))
+                fields.append((ctype, name, None if length is None else int(length) if length.isdigit() else constants[length] if length in constants or not scope else scope[length]))
         return " "
     text = re.sub(r"typedef\s+struct\b[^{;]*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
 
@@ -84,6 +85,23 @@ def header():
                                "and has no table of its own") from e
         _header = parse(text)
     return _header
+
+
+_extensions = {}
+
+
+def extension(name):
+    """parse() of include/<name>, an extension family's header (gsraster_jpeg_decode.h), with header()'s constants in scope; read once
+    per process.  header() itself -- the main header's functions, constants and structs -- is what it was."""
+    if name not in _extensions:
+        path = os.path.join(os.path.dirname(HEADER_PATH), name)
+        try:
+            with open(path) as f:
+                text = f.read()
+        except OSError as e:
+            raise RuntimeError(f"gscream_amd: the C ABI header {path} cannot be read ({e}); the binding is derived from it") from e
+        _extensions[name] = parse(text, header().constants)
+    return _extensions[name]
 
 
 def ctype(decl, structs=(), returns=False):

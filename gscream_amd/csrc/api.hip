@@ -1414,6 +1414,42 @@ extern "C" int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png
     return GSR_OK;
 }
 
+// ---- JPEG decoding (jpeg_decode.hip; declared in include/gsraster_jpeg_decode.h) ----
+extern "C" size_t gsr_jpeg_decode_workspace_bytes(size_t area_bytes, int nfiles, int nintervals)
+{
+    if (nfiles <= 0 || nintervals <= 0 || area_bytes >= ((size_t)1 << 40)) return 0;  // (no accepted size wraps the carve: 2^40 + 2^31 * 16)
+    return jpeg_decode_workspace_bytes(area_bytes, nintervals);
+}
+
+extern "C" int gsr_jpeg_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant,
+                               int nquant, const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status,
+                               void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!bytes || !files || !quant || !huffman || !out || !status || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: bytes, files, quant, huffman, out, status or workspace is NULL");
+    if (nfiles <= 0 || nintervals <= 0 || nquant <= 0 || nhuffman <= 0 || nfiles > 65535)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: nfiles=%d nintervals=%d nquant=%d nhuffman=%d (need all > 0, nfiles <= 65535)", nfiles,
+                        nintervals, nquant, nhuffman);
+    if (nbytes >= ((size_t)1 << 32) || out_bytes >= ((size_t)1 << 32))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: nbytes=%zu out_bytes=%zu (need both < 2^32)", nbytes, out_bytes);
+    if (((uintptr_t)bytes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)quant & 15) || ((uintptr_t)files & 7) ||
+        ((uintptr_t)status & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: bytes, out, workspace and quant are 16-byte aligned, files 8, status 4");
+    if (workspace_bytes < jd_tables_bytes(nintervals))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
+    GSR_HIP(jpeg_launch_decode(bytes, nbytes, files, nfiles, nintervals, quant, nquant, huffman, nhuffman, out, out_bytes, status, workspace,
+                               workspace_bytes, (hipStream_t)stream),
+            "jpeg decode");
+    return GSR_OK;
+}
+
+extern "C" const char* gsr_jpeg_decode_status_name(int code)
+{
+    static const char* const names[] = {"ok", "truncated", "bit pattern with no symbol", "invalid symbol", "run past coefficient 63",
+                                        "restart markers miscounted, misnumbered or misplaced", "table entry out of bounds"};
+    return code >= GSR_JPEG_DECODE_OK && code <= GSR_JPEG_DECODE_TABLE ? names[code] : "?";
+}
+
 // ---- resize (resize.hip) ----
 static int resize_check(const char* what, const void* src, const void* out, long long src_image_stride, long long src_row_stride, int n, int H, int W,
                         int C, int H_out, int W_out, long long out_image_stride, long long out_row_stride, int epilogue)

@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/gsraster.h"
+#include "../../include/gsraster_jpeg_decode.h"
 #include "gsr_carve.h"
 
 #define GSR_TILE 16
@@ -570,6 +571,15 @@ size_t pd_tables_bytes(int nfiles, int npieces);  // the tables' part alone: the
 hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                              hipStream_t stream);
+
+// jpeg_decode.hip: baseline JPEG files -> uint8 pictures (pointers and counts validated by the caller; the tables are checked on the
+// device).  The workspace holds the caller's area (the files' coefficients and component planes), then per restart interval {start, end,
+// status, owner}.
+size_t jpeg_decode_workspace_bytes(size_t area_bytes, int nintervals);
+size_t jd_tables_bytes(int nintervals);  // the tables' part alone: the least workspace a call is taken with
+hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
+                              const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
+                              size_t workspace_bytes, hipStream_t stream);
 
 // resize.hip: PIL's Image.resize, one pass (or one NEAREST gather) per launch (validated by the caller)
 hipError_t resize_launch_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis,

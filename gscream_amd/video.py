@@ -11,14 +11,17 @@ below and decode every frame with PIL (INTEGRATION Y).
     24 bits, MJPG) } }, LIST 'movi' { '00dc' chunk per frame: one JPEG file, padded to even length with a zero }, 'idx1' { 16 bytes
     per frame: '00dc', AVIIF_KEYFRAME, the chunk's offset from the 'movi' fourcc, its size } }
 
-All numbers little-endian.  A file stays below 2^31 - 1 bytes (no OpenDML): `add` refuses the frame that would pass it."""
+All numbers little-endian.  A file stays below 2^31 - 1 bytes (no OpenDML): `add` refuses the frame that would pass it.
+
+Reading it back: MjpegReader walks the 'movi' list of such a file chunk by chunk (the index is not needed) and decodes the frames with
+gscream_amd.jpeg_decode, a batch per call, on the device; read_rgbd_video returns all of them (INTEGRATION Z)."""
 import struct
 
 import torch
 
 from . import jpeg
 
-__all__ = ["MjpegWriter", "save_rgbd_video"]
+__all__ = ["MjpegReader", "MjpegWriter", "read_rgbd_video", "save_rgbd_video"]
 
 AVIF_HASINDEX, AVIIF_KEYFRAME = 0x10, 0x10
 MAX_BYTES = (1 << 31) - 1
@@ -114,3 +117,74 @@ def save_rgbd_video(sheets, path, fps=25, quality=95, batch=8):
     finally:
         if writer is not None:
             writer.close()
+
+
+class MjpegReader:
+    """MjpegReader(path): the frames of a file MjpegWriter wrote.  W, H, fps from the headers; len() frames; frames(device, batch)
+    yields uint8 [H, W, 3] pictures in order, `batch` files per jpeg_decode.decode + check, the pictures staying on `device`.  The
+    'movi' list is walked by its chunk sizes; 'idx1' is not read.  ValueError for a file that is not RIFF 'AVI ' with an MJPG stream
+    first, or whose chunks run past the list."""
+
+    def __init__(self, path):
+        with open(path, "rb") as f:
+            data = f.read()
+        self.path = path
+
+        def bad(reason):
+            return ValueError(f"MjpegReader: {path}: {reason}")
+        if len(data) < _HEAD or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+            raise bad("not a RIFF 'AVI ' file")
+        at, end = 12, min(len(data), 8 + struct.unpack_from("<I", data, 4)[0])
+        self.W = self.H = self.fps = None
+        self.chunks = []  # (offset of the JPEG file, size)
+        movi = False
+        while at + 8 <= end and not movi:
+            kind, size = struct.unpack_from("<4sI", data, at)
+            if kind == b"LIST" and data[at + 8:at + 12] == b"hdrl":
+                avih = at + 12
+                if data[avih:avih + 4] != b"avih" or struct.unpack_from("<I", data, avih + 4)[0] < 40:
+                    raise bad("'hdrl' does not start with an 'avih' chunk")
+                self.W, self.H = struct.unpack_from("<II", data, avih + 8 + 32)
+                strl = avih + 8 + struct.unpack_from("<I", data, avih + 4)[0]
+                if data[strl:strl + 4] != b"LIST" or data[strl + 8:strl + 16] != b"strlstrh" or data[strl + 20:strl + 28] != b"vidsMJPG":
+                    raise bad("the first stream is not Motion-JPEG video")
+                scale, rate = struct.unpack_from("<II", data, strl + 20 + 20)
+                self.fps = rate / scale if scale else float(rate)
+            elif kind == b"LIST" and data[at + 8:at + 12] == b"movi":
+                movi = True
+                stop, q = min(end, at + 8 + size), at + 12
+                while q + 8 <= stop:
+                    tag, n = struct.unpack_from("<4sI", data, q)
+                    if q + 8 + n > stop:
+                        raise bad("a chunk runs past the 'movi' list")
+                    if tag == b"00dc" and n:
+                        self.chunks.append((q + 8, n))
+                    q += 8 + n + (n & 1)
+            at += 8 + size + (size & 1)
+        if not movi or self.W is None:
+            raise bad("no 'hdrl' or no 'movi' list")
+        self.data = data
+
+    def __len__(self):
+        return len(self.chunks)
+
+    def frame_bytes(self, i):
+        off, n = self.chunks[i]
+        return self.data[off:off + n]
+
+    def frames(self, device, batch=8):
+        from . import jpeg_decode
+        if batch < 1:
+            raise ValueError(f"MjpegReader: batch={batch!r} (need >= 1)")
+        for at in range(0, len(self.chunks), batch):
+            ids = range(at, min(at + batch, len(self.chunks)))
+            pictures = jpeg_decode.check(jpeg_decode.decode([self.frame_bytes(i) for i in ids], device, [f"{self.path} frame {i}" for i in ids]))
+            for image in pictures.images:
+                if tuple(image.shape) != (self.H, self.W, 3):
+                    raise ValueError(f"MjpegReader: {self.path}: a frame of {tuple(image.shape)} in a {self.H} x {self.W} stream")
+                yield image
+
+
+def read_rgbd_video(path, device, batch=8):
+    """All frames of a save_rgbd_video / MjpegWriter file -> the list of uint8 [H, W, 3] pictures on `device`."""
+    return list(MjpegReader(path).frames(device, batch))
