@@ -5,7 +5,7 @@ library is missing or a call fails, a RuntimeError is raised -- the product path
 through the CPU oracle or through eager PyTorch.
 
 The header is the source of this binding (_abi.py reads it): a new entry point or constant is an edit of
-include/gsraster.h and api.hip, and of nothing here unless a wrapper wants the constant under a name of its own (_CONSTANTS).
+include/gsraster.h and the module's own .hip file (its C entry points are at the file's end), and of nothing here unless a wrapper wants the constant under a name of its own (_CONSTANTS).
 """
 import ctypes
 import os

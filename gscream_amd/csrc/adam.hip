@@ -27,7 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
 
 #pragma clang fp contract(off)
 
@@ -148,8 +148,21 @@ static int adam_unit(const gsr_adam_tensor& t)
     return bits % 16 == 0 ? 4 : 1;
 }
 
-hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, void* stream)
 {
+    if (n_tensors < 0 || n_tensors > GSR_ADAM_MAX_TENSORS)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: n_tensors=%d (need 0 .. %d)", n_tensors, GSR_ADAM_MAX_TENSORS);
+    if (n_tensors == 0) return GSR_OK;
+    if (!tensors) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensors is NULL");
+    for (int c = 0; c < n_tensors; c++) {
+        const gsr_adam_tensor& t = tensors[c];
+        if (t.n < 0 || t.n > 0x7fffff00)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a bad size n=%d (need 0 <= n <= 2^31 - 256)", c, t.n);
+        if (t.n > 0 && (!t.p || !t.g || !t.m || !t.v)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a NULL pointer", c);
+        if (t.n > 0 && (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "adam step: tensor %d has a pointer that is not 4-byte aligned", c);
+    }
     AdamTable tab{};
     uint32_t blocks = 0;
     int used = 0;
@@ -163,9 +176,10 @@ hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_
         blocks += (units + ADAM_CHUNK - 1u) / ADAM_CHUNK;                                      // <= 32 * 2^21 in all
         used++;
     }
-    if (used == 0) return hipSuccess;
+    if (used == 0) return GSR_OK;
     tab.first[used] = blocks;
     tab.n = used;
-    hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, stream, tab);
-    return hipGetLastError();
+    hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, tab);
+    GSR_HIP(hipGetLastError(), "adam step");
+    return GSR_OK;
 }

@@ -18,7 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 
 #define GAA_THREADS 256                      // anchors per block of the flag / place kernels (one per thread)
@@ -101,30 +102,6 @@ static GaaWork gaa_carve(void* base, int N)
     w.keep = c.take<uint8_t>((size_t)N);
     w.bytes = c.total();
     return w;
-}
-
-size_t gaa_workspace_bytes(int N) { return gaa_carve(nullptr, N).bytes; }
-
-hipError_t gaa_launch_offsets(int L0, const float* accum, const float* denom, float thr_half, float* grads_norm, uint8_t* offset_mask,
-                              hipStream_t stream)
-{
-    if (L0 == 0) return hipSuccess;
-    hipLaunchKernelGGL(gaa_offsets_kernel, dim3(gaa_blocks(L0, GAA_THREADS)), dim3(GAA_THREADS), 0, stream, L0, accum, denom, thr_half,
-                       grads_norm, offset_mask);
-    return hipGetLastError();
-}
-
-hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask, float min_opacity, float thr,
-                           void* workspace, int32_t* keep_rows, uint8_t* reset, int32_t* info, hipStream_t stream)
-{
-    if (N == 0) return hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream);
-    const GaaWork w = gaa_carve(workspace, N);
-    const int nb = gaa_blocks(N, GAA_THREADS);
-    hipLaunchKernelGGL(gaa_flag_kernel, dim3(nb), dim3(GAA_THREADS), 0, stream, N, opacity_accum, anchor_demon, prune_mask, min_opacity, thr,
-                       w.keep, reset, w.block_sum);
-    hipLaunchKernelGGL(gaa_top_scan_kernel, dim3(1), dim3(1024), 0, stream, N, nb, w.block_sum, info);
-    hipLaunchKernelGGL(gaa_place_kernel, dim3(nb), dim3(GAA_THREADS), 0, stream, N, w.keep, w.block_sum, keep_rows);
-    return hipGetLastError();
 }
 
 // ---- gather ----------------------------------------------------------------------------------------------------------------
@@ -222,10 +199,66 @@ static int gaa_unit(const gsr_adjust_copy& d)
     return 1;
 }
 
-hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows, const uint8_t* offset_mask,
-                             int L0, const uint8_t* reset, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_anchor_adjust_workspace_bytes(int N)
 {
-    if (n_keep == 0 || n_copies == 0) return hipSuccess;
+    if (N < 0 || N > 0x7fffff00) return 0;  // (no accepted N wraps the carve: N bytes + N / 256 sums)
+    return gaa_carve(nullptr, N).bytes;
+}
+
+extern "C" int gsr_anchor_adjust_offsets(int L0, const float* offset_gradient_accum, const float* offset_denom, float denom_threshold,
+                                         float* grads_norm, uint8_t* offset_mask, void* stream)
+{
+    if (L0 < 0 || L0 > 0x7fffff00) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust offsets: bad size L0=%d", L0);
+    if (L0 > 0 && (!offset_gradient_accum || !offset_denom || !grads_norm || !offset_mask))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust offsets: a required pointer is NULL");
+    if (L0 == 0) return GSR_OK;
+    hipLaunchKernelGGL(gaa_offsets_kernel, dim3(gaa_blocks(L0, GAA_THREADS)), dim3(GAA_THREADS), 0, (hipStream_t)stream, L0, offset_gradient_accum,
+                       offset_denom, denom_threshold, grads_norm, offset_mask);
+    GSR_HIP(hipGetLastError(), "anchor adjust offsets");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_adjust_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask,
+                                      float min_opacity, float demon_threshold, void* workspace, int32_t* keep_rows, uint8_t* reset,
+                                      int32_t* info, void* stream_)
+{
+    if (N < 0 || N > 0x7fffff00) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust plan: bad size N=%d", N);
+    if (!info || (N > 0 && (!workspace || !keep_rows || !reset || (!prune_mask && (!opacity_accum || !anchor_demon)))))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust plan: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N == 0) { GSR_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream), "anchor adjust plan"); return GSR_OK; }
+    const GaaWork w = gaa_carve(workspace, N);
+    const int nb = gaa_blocks(N, GAA_THREADS);
+    hipLaunchKernelGGL(gaa_flag_kernel, dim3(nb), dim3(GAA_THREADS), 0, stream, N, opacity_accum, anchor_demon, prune_mask, min_opacity, demon_threshold,
+                       w.keep, reset, w.block_sum);
+    hipLaunchKernelGGL(gaa_top_scan_kernel, dim3(1), dim3(1024), 0, stream, N, nb, w.block_sum, info);
+    hipLaunchKernelGGL(gaa_place_kernel, dim3(nb), dim3(GAA_THREADS), 0, stream, N, w.keep, w.block_sum, keep_rows);
+    GSR_HIP(hipGetLastError(), "anchor adjust plan");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_adjust_gather(int N, int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows,
+                                        const uint8_t* offset_mask, int L0, const uint8_t* reset, void* stream)
+{
+    if (N < 0 || n_keep < 0 || n_keep > N || n_copies < 0 || n_copies > GSR_ADJUST_MAX_COPIES || L0 < 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: bad sizes N=%d n_keep=%d n_copies=%d L0=%d", N, n_keep, n_copies, L0);
+    if (n_keep == 0 || n_copies == 0) return GSR_OK;
+    if (!copies || !keep_rows) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copies / keep_rows is NULL");
+    for (int c = 0; c < n_copies; c++) {
+        const gsr_adjust_copy& d = copies[c];
+        if (d.width < 1 || (long long)N * d.width > 0x7fffffffLL || d.mode < GSR_ADJUST_COPY || d.mode > GSR_ADJUST_ANCHOR_STAT)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d has width %d, mode %d (need 1 <= width, N*width < 2^31)", c,
+                            d.width, d.mode);
+        if (!d.dst || (!d.src && !(d.mode == GSR_ADJUST_OFFSET_STAT && L0 == 0)))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d has a NULL pointer", c);
+        if (d.mode == GSR_ADJUST_OFFSET_STAT && L0 > 0 && !offset_mask)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d is OFFSET_STAT but offset_mask is NULL", c);
+        if (d.mode == GSR_ADJUST_OFFSET_STAT && (long long)L0 > (long long)N * d.width)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: L0=%d exceeds N*K=%lld", L0, (long long)N * d.width);
+        if (d.mode == GSR_ADJUST_ANCHOR_STAT && (d.width != 1 || !reset))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor adjust gather: copy %d is ANCHOR_STAT: width must be 1 and reset given", c);
+    }
     GaaTable tab{};
     tab.n = n_copies;
     uint32_t blocks = 0;
@@ -236,6 +269,7 @@ hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* co
         blocks += (uint32_t)gaa_blocks((long long)n_keep * (copies[c].width / tab.vec[c]), GAA_CHUNK);
     }
     tab.first[n_copies] = blocks;
-    hipLaunchKernelGGL(gaa_gather_kernel, dim3(blocks), dim3(GAA_THREADS), 0, stream, tab, n_keep, keep_rows, offset_mask, L0, reset);
-    return hipGetLastError();
+    hipLaunchKernelGGL(gaa_gather_kernel, dim3(blocks), dim3(GAA_THREADS), 0, (hipStream_t)stream, tab, n_keep, keep_rows, offset_mask, L0, reset);
+    GSR_HIP(hipGetLastError(), "anchor adjust gather");
+    return GSR_OK;
 }

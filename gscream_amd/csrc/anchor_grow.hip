@@ -28,7 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 
 #define GAG_THREADS 256
@@ -291,54 +292,6 @@ static GagWork gag_carve(void* base, int N, int L)
     return w;
 }
 
-size_t gag_workspace_bytes(int N, int L) { return gag_carve(nullptr, N, L).bytes; }
-
-hipError_t gag_launch_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling, const uint8_t* mask, float inv,
-                           void* workspace, int64_t* keys, int32_t* rows, int32_t* info, hipStream_t stream)
-{
-    const GagWork w = gag_carve(workspace, N, L);
-    hipError_t e;
-    if ((e = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.table, 0xff, (size_t)w.cap * 4, stream)) != hipSuccess) return e;
-    if (N > 0) {
-        hipLaunchKernelGGL(gag_anchor_cells_kernel, dim3(gag_blocks(N)), dim3(GAG_THREADS), 0, stream, N, anchor, inv, w.cells, info);
-        hipLaunchKernelGGL(gag_insert_kernel, dim3(gag_blocks(N)), dim3(GAG_THREADS), 0, stream, N, w.cells, w.table, w.cap - 1u);
-    }
-    if (L > 0) {
-        const int nb = gag_blocks(L);
-        hipLaunchKernelGGL(gag_mask_count_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, L, mask, w.block_sum);
-        hipLaunchKernelGGL(gag_top_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, w.block_sum, info, (int32_t*)nullptr);
-        hipLaunchKernelGGL(gag_place_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, L, K, mask, w.block_sum, anchor, offset, scaling, inv,
-                           keys, rows, info);
-    }
-    return hipGetLastError();
-}
-
-hipError_t gag_launch_emit(int N, int K, int F, int L, int M, const float* feat, const int64_t* sorted_keys, const int64_t* perm,
-                           const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor, float* new_feat, int32_t* info,
-                           hipStream_t stream)
-{
-    const GagWork w = gag_carve(workspace, N, L);
-    hipError_t e;
-    if ((e = hipMemsetAsync(info + 2, 0, sizeof(int32_t), stream)) != hipSuccess) return e;
-    if (M <= 0) return hipSuccess;
-    if ((e = hipMemsetAsync(new_feat, 0, (size_t)M * F * 4, stream)) != hipSuccess) return e;
-    const int nb = gag_blocks(M);
-    hipLaunchKernelGGL(gag_head_count_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, sorted_keys, w.cells, w.table, w.cap - 1u,
-                       w.head_kind, w.block_sum);
-    hipLaunchKernelGGL(gag_top_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, w.block_sum, (int32_t*)nullptr, info + 2);
-    hipLaunchKernelGGL(gag_head_place_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, sorted_keys, w.head_kind, w.block_sum, cur_size,
-                       w.pos_seg, w.seg_slot, candidate_anchor);
-    if (F > 0) {
-        hipLaunchKernelGGL(gag_feat_max_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, K, F, perm, rows, w.pos_seg, w.seg_slot, feat,
-                           (uint32_t*)new_feat);
-        const size_t n = (size_t)M * F;
-        hipLaunchKernelGGL(gag_decode_kernel, dim3((unsigned)((n + GAG_THREADS - 1) / GAG_THREADS)), dim3(GAG_THREADS), 0, stream, n,
-                           (uint32_t*)new_feat);
-    }
-    return hipGetLastError();
-}
-
 // ---- scatter_max along dim 0 with a row index: out[index[r], f] = max_r src[r, f]; argmax = smallest such r ---------------
 __global__ void __launch_bounds__(GAG_THREADS) gag_smax_max_kernel(int R, int F, int S, const float* __restrict__ src, const int64_t* __restrict__ index,
                                                                    uint32_t* __restrict__ code)
@@ -370,12 +323,87 @@ __global__ void __launch_bounds__(GAG_THREADS) gag_smax_fill_kernel(size_t n, in
     if (i < n) argmax[i] = fill;
 }
 
-hipError_t gag_launch_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_anchor_grow_workspace_bytes(int N, int L)
 {
+    if (N < 0 || L < 0) return 0;
+    return gag_carve(nullptr, N, L).bytes;
+}
+
+static int gag_check_sizes(const char* what, int N, int K, int L)
+{
+    if (N < 0 || K < 1 || L < 0 || (long long)L > (long long)N * K || L > 0x7fffff00)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes N=%d K=%d L=%d (need 0 <= L <= N*K < 2^31)", what, N, K, L);
+    // (no accepted size wraps the carve: 3 N cells and L slots of 4 bytes, below 2^35)
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_grow_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling,
+                                    const uint8_t* candidate_mask, float inv_size, void* workspace, int64_t* keys, int32_t* rows,
+                                    int32_t* info, void* stream_)
+{
+    if (int rc = gag_check_sizes("anchor grow keys", N, K, L)) return rc;
+    if (!workspace || !info || (N > 0 && !anchor) || (L > 0 && (!offset || !scaling || !candidate_mask || !keys || !rows)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow keys: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    const GagWork w = gag_carve(workspace, N, L);
+    GSR_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream), "anchor grow keys");
+    GSR_HIP(hipMemsetAsync(w.table, 0xff, (size_t)w.cap * 4, stream), "anchor grow keys");
+    if (N > 0) {
+        hipLaunchKernelGGL(gag_anchor_cells_kernel, dim3(gag_blocks(N)), dim3(GAG_THREADS), 0, stream, N, anchor, inv_size, w.cells, info);
+        hipLaunchKernelGGL(gag_insert_kernel, dim3(gag_blocks(N)), dim3(GAG_THREADS), 0, stream, N, w.cells, w.table, w.cap - 1u);
+    }
+    if (L > 0) {
+        const int nb = gag_blocks(L);
+        hipLaunchKernelGGL(gag_mask_count_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, L, candidate_mask, w.block_sum);
+        hipLaunchKernelGGL(gag_top_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, w.block_sum, info, (int32_t*)nullptr);
+        hipLaunchKernelGGL(gag_place_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, L, K, candidate_mask, w.block_sum, anchor, offset, scaling, inv_size,
+                           keys, rows, info);
+    }
+    GSR_HIP(hipGetLastError(), "anchor grow keys");
+    return GSR_OK;
+}
+
+extern "C" int gsr_anchor_grow_emit(int N, int K, int F, int L, int M, const float* anchor_feat, const int64_t* sorted_keys,
+                                    const int64_t* order, const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor,
+                                    float* new_feat, int32_t* info, void* stream_)
+{
+    if (int rc = gag_check_sizes("anchor grow emit", N, K, L)) return rc;
+    if (F < 0 || M < 0 || M > L) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow emit: bad sizes F=%d M=%d L=%d", F, M, L);
+    if (!workspace || !info || (M > 0 && (!sorted_keys || !order || !rows || !candidate_anchor || (F > 0 && (!anchor_feat || !new_feat)))))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor grow emit: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    const GagWork w = gag_carve(workspace, N, L);
+    GSR_HIP(hipMemsetAsync(info + 2, 0, sizeof(int32_t), stream), "anchor grow emit");
+    if (M <= 0) return GSR_OK;
+    GSR_HIP(hipMemsetAsync(new_feat, 0, (size_t)M * F * 4, stream), "anchor grow emit");
+    const int nb = gag_blocks(M);
+    hipLaunchKernelGGL(gag_head_count_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, sorted_keys, w.cells, w.table, w.cap - 1u,
+                       w.head_kind, w.block_sum);
+    hipLaunchKernelGGL(gag_top_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, w.block_sum, (int32_t*)nullptr, info + 2);
+    hipLaunchKernelGGL(gag_head_place_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, sorted_keys, w.head_kind, w.block_sum, cur_size,
+                       w.pos_seg, w.seg_slot, candidate_anchor);
+    if (F > 0) {
+        hipLaunchKernelGGL(gag_feat_max_kernel, dim3(nb), dim3(GAG_THREADS), 0, stream, M, K, F, order, rows, w.pos_seg, w.seg_slot, anchor_feat,
+                           (uint32_t*)new_feat);
+        const size_t n = (size_t)M * F;
+        hipLaunchKernelGGL(gag_decode_kernel, dim3((unsigned)((n + GAG_THREADS - 1) / GAG_THREADS)), dim3(GAG_THREADS), 0, stream, n,
+                           (uint32_t*)new_feat);
+    }
+    GSR_HIP(hipGetLastError(), "anchor grow emit");
+    return GSR_OK;
+}
+
+extern "C" int gsr_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, void* stream_)
+{
+    if (R < 0 || F < 0 || S < 0 || (long long)R * F > (1ll << 40) || (long long)S * F > (1ll << 40))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: bad sizes R=%d F=%d S=%d", R, F, S);
+    if ((long long)S * F > 0 && (!out || !argmax)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: out / argmax is NULL");
+    if ((long long)R * F > 0 && (long long)S * F > 0 && (!src || !index)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scatter_max: src / index is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
     const size_t n_out = (size_t)S * F, n_in = (size_t)R * F;
-    hipError_t e;
-    if (n_out == 0) return hipSuccess;
-    if ((e = hipMemsetAsync(out, 0, n_out * 4, stream)) != hipSuccess) return e;
+    if (n_out == 0) return GSR_OK;
+    GSR_HIP(hipMemsetAsync(out, 0, n_out * 4, stream), "scatter_max");
     const unsigned gout = (unsigned)((n_out + GAG_THREADS - 1) / GAG_THREADS), gin = (unsigned)((n_in + GAG_THREADS - 1) / GAG_THREADS);
     hipLaunchKernelGGL(gag_smax_fill_kernel, dim3(gout), dim3(GAG_THREADS), 0, stream, n_out, (int64_t)R, argmax);
     if (n_in > 0) {
@@ -383,5 +411,6 @@ hipError_t gag_launch_scatter_max(int R, int F, int S, const float* src, const i
         hipLaunchKernelGGL(gag_smax_arg_kernel, dim3(gin), dim3(GAG_THREADS), 0, stream, R, F, S, src, index, (const uint32_t*)out, argmax);
     }
     hipLaunchKernelGGL(gag_decode_kernel, dim3(gout), dim3(GAG_THREADS), 0, stream, n_out, (uint32_t*)out);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "scatter_max");
+    return GSR_OK;
 }

@@ -30,7 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 
 #define GAS_THREADS 256
@@ -288,22 +289,35 @@ static GasWork gas_carve(void* base, int N)
     return w;
 }
 
-size_t gas_workspace_bytes(int N, int max_pairs)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int gas_check_sizes(int N, int H, int W, int max_pairs)
 {
-    (void)max_pairs;  // the row lists are the caller's; the argument keeps the size query's signature in step with the call's
-    return gas_carve(nullptr, N).bytes;
+    if (N < 0 || N > 0x7fffff00 || max_pairs < 0 || H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || (long long)H * W > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor sample: bad sizes N=%d H=%d W=%d max_pairs=%d", N, H, W, max_pairs);
+    // (no accepted size wraps the carve: N < 2^31 bytes per array)
+    return GSR_OK;
 }
 
-hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask, int min_y,
-                      int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace, uint8_t* src_mask, uint8_t* dst_mask,
-                      int64_t* src_rows, int64_t* dst_rows, int32_t* info, hipStream_t stream)
+extern "C" size_t gsr_anchor_sample_workspace_bytes(int N, int max_pairs)
 {
-    hipError_t e;
-    if (N == 0) return hipMemsetAsync(info, 0, 8 * sizeof(int32_t), stream);
+    if (N < 0 || N > 0x7fffff00 || max_pairs < 0) return 0;
+    return gas_carve(nullptr, N).bytes;  // (the row lists are the caller's; max_pairs keeps the size query's signature in step with the call's)
+}
+
+extern "C" int gsr_anchor_sample(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask,
+                                 int min_y, int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace,
+                                 uint8_t* src_mask, uint8_t* dst_mask, int64_t* src_rows, int64_t* dst_rows, int32_t* info, void* stream_)
+{
+    if (int rc = gas_check_sizes(N, H, W, max_pairs)) return rc;
+    if (!info || (N > 0 && (!workspace || !visible || !px || !py || !gt_mask || !src_mask || !dst_mask))
+        || (N > 0 && max_pairs > 0 && (!src_rows || !dst_rows)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "anchor sample: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N == 0) { GSR_HIP(hipMemsetAsync(info, 0, 8 * sizeof(int32_t), stream), "anchor sample"); return GSR_OK; }
     const GasWork w = gas_carve(workspace, N);
     const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
     const int nt = gas_blocks(N, GAS_TILE), nb = gas_blocks(N, GAS_THREADS);
-    if ((e = hipMemsetAsync(w.head, 0, (size_t)GAS_HEAD_WORDS * 4, stream)) != hipSuccess) return e;
+    GSR_HIP(hipMemsetAsync(w.head, 0, (size_t)GAS_HEAD_WORDS * 4, stream), "anchor sample");
     hipLaunchKernelGGL(gas_classify_kernel, dim3(nt), dim3(GAS_THREADS), 0, stream, N, H, W, visible, px, py, gt_mask, min_y, max_y, min_x,
                        max_x, s_lo, s_hi, w.cls, w.head);
     hipLaunchKernelGGL(gas_pick_kernel, dim3(1), dim3(1024), 0, stream, 0, max_pairs, w.head, info);
@@ -315,5 +329,6 @@ hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* 
     hipLaunchKernelGGL(gas_top_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, w.sum_fg, w.sum_bg);
     hipLaunchKernelGGL(gas_place_kernel, dim3(nb), dim3(GAS_THREADS), 0, stream, N, max_pairs, w.flag, w.head, w.sum_fg, w.sum_bg, src_mask,
                        dst_mask, src_rows, dst_rows);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "anchor sample");
+    return GSR_OK;
 }

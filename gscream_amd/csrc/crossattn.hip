@@ -24,7 +24,8 @@
 // Sums run in a fixed order and nothing is accumulated with atomics: two calls on the same inputs give the same bits.
 #include <float.h>
 #include <math.h>
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 
 typedef float gca_v16 __attribute__((ext_vector_type(16)));
 typedef float gca_v4 __attribute__((ext_vector_type(4)));
@@ -383,8 +384,6 @@ static GcaWork gca_carve(void* base, int B, int H, int I, int J)
     return w;
 }
 
-size_t gca_workspace_bytes(int B, int H, int I, int J) { return gca_carve(nullptr, B, H, I, J).bytes; }
-
 static GcaArgs gca_args(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv, const uint8_t* mask,
                         const uint8_t* cmask, float scale, void* workspace)
 {
@@ -403,32 +402,57 @@ static dim3 gca_grid(int B, int H, int I, int J)
     return dim3((n + GCA_ROWS - 1) / GCA_ROWS, B * H, 2);
 }
 
-hipError_t gca_launch_forward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
-                              const uint8_t* mask, const uint8_t* cmask, float scale, float* out, float* cout, void* workspace,
-                              hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int gca_check_sizes(const char* what, int B, int H, int I, int J, int dim_head)
 {
-    GcaArgs a = gca_args(B, H, I, J, qk, v, cqk, cv, mask, cmask, scale, workspace);
-    a.s[0].out = out;
-    a.s[1].out = cout;
-    hipLaunchKernelGGL(gca_forward_kernel, gca_grid(B, H, I, J), dim3(GCA_THREADS), 0, stream, a);
-    return hipGetLastError();
+    if (dim_head != 64) return gsr_fail(GSR_ERR_UNSUPPORTED, "%s: dim_head = %d (this path is built for 64)", what, dim_head);
+    if (B < 1 || H < 1 || I < 1 || J < 1 || (long long)B * H > 65535 || (long long)B * H * ((long long)I + J) * 64 > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes b=%d heads=%d i=%d j=%d", what, B, H, I, J);
+    // (no accepted size wraps the carve: B*H*(I + J) < 2^25 rows of 12 bytes)
+    return GSR_OK;
 }
 
-hipError_t gca_launch_backward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
-                               const uint8_t* mask, const uint8_t* cmask, float scale, const float* out, const float* cout,
-                               const float* d_out, const float* d_cout, void* workspace, float* d_qk, float* d_v, float* d_cqk,
-                               float* d_cv, hipStream_t stream)
+extern "C" size_t gsr_crossattn_workspace_bytes(int B, int H, int I, int J)
 {
-    GcaArgs a = gca_args(B, H, I, J, qk, v, cqk, cv, mask, cmask, scale, workspace);
+    if (B < 1 || H < 1 || I < 1 || J < 1) return 0;
+    return gca_carve(nullptr, B, H, I, J).bytes;
+}
+
+extern "C" int gsr_crossattn_forward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                                     const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale, float* out,
+                                     float* context_out, void* workspace, void* stream)
+{
+    if (int rc = gca_check_sizes("crossattn forward", B, H, I, J, dim_head)) return rc;
+    if (!qk || !v || !context_qk || !context_v || !out || !context_out || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "crossattn forward: a required pointer is NULL");
+    GcaArgs a = gca_args(B, H, I, J, qk, v, context_qk, context_v, mask, context_mask, scale, workspace);
+    a.s[0].out = out;
+    a.s[1].out = context_out;
+    hipLaunchKernelGGL(gca_forward_kernel, gca_grid(B, H, I, J), dim3(GCA_THREADS), 0, (hipStream_t)stream, a);
+    GSR_HIP(hipGetLastError(), "crossattn forward");
+    return GSR_OK;
+}
+
+extern "C" int gsr_crossattn_backward(int B, int H, int I, int J, int dim_head, const float* qk, const float* v, const float* context_qk,
+                                      const float* context_v, const uint8_t* mask, const uint8_t* context_mask, float scale,
+                                      const float* out, const float* context_out, const float* d_out, const float* d_context_out,
+                                      void* workspace, float* d_qk, float* d_v, float* d_context_qk, float* d_context_v, void* stream_)
+{
+    if (int rc = gca_check_sizes("crossattn backward", B, H, I, J, dim_head)) return rc;
+    if (!qk || !v || !context_qk || !context_v || !out || !context_out || !d_out || !d_context_out || !workspace || !d_qk || !d_v
+        || !d_context_qk || !d_context_v)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "crossattn backward: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    GcaArgs a = gca_args(B, H, I, J, qk, v, context_qk, context_v, mask, context_mask, scale, workspace);
     a.s[0].out = const_cast<float*>(out);
-    a.s[1].out = const_cast<float*>(cout);
+    a.s[1].out = const_cast<float*>(context_out);
     a.s[0].d_out = d_out;
-    a.s[1].d_out = d_cout;
+    a.s[1].d_out = d_context_out;
     a.s[0].d_qk = d_qk; a.s[0].d_v = d_v;
-    a.s[1].d_qk = d_cqk; a.s[1].d_v = d_cv;
+    a.s[1].d_qk = d_context_qk; a.s[1].d_v = d_context_v;
     hipLaunchKernelGGL(gca_rowdot_kernel, gca_grid(B, H, I, J), dim3(GCA_THREADS), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    GSR_HIP(hipGetLastError(), "crossattn backward");
     hipLaunchKernelGGL(gca_backward_kernel, gca_grid(B, H, I, J), dim3(GCA_THREADS), 0, stream, a);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "crossattn backward");
+    return GSR_OK;
 }

@@ -26,7 +26,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
 #include "gsr_math.h"
 #include "gsr_scan.h"
 
@@ -939,40 +939,12 @@ static GsdMlps gsd_pack(const float* const* w)  // w[16] = {w1[4], b1[4], w2[4],
     return P;
 }
 
-hipError_t gsd_launch_count(int N, int K, const float* const* weights, const int32_t* vis, const uint32_t* vis_count, const float* feat, const float* anchor,
-                            const float* campos, float* neural_opacity, uint8_t* mask, uint8_t* count, uint32_t* first,
-                            uint32_t* total, uint32_t* block_scratch, hipStream_t stream)
-{
-    if (N <= 0) return hipSuccess;
-    const int nb = (N + GSD_THREADS - 1) / GSD_THREADS;
-    hipLaunchKernelGGL(gsd_count_kernel, dim3(nb < 8 * GSD_MLP_GRID ? nb : 8 * GSD_MLP_GRID), dim3(GSD_THREADS), 0, stream, N, K, gsd_pack(weights), vis, vis_count, feat, anchor, campos,
-                       neural_opacity, mask, count, block_scratch);
-    hipLaunchKernelGGL(gsd_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, block_scratch, total);
-    hipLaunchKernelGGL(gsd_first_kernel, dim3(nb), dim3(GSD_THREADS), 0, stream, N, count, block_scratch, first);
-    return hipGetLastError();
-}
-
-hipError_t gsd_launch_emit(int N, int K, const float* const* weights, const int32_t* vis, const uint32_t* vis_count, const float* feat, const float* anchor,
-                           const float* offsets, const float* gscale, const float* campos, const float* neural_opacity,
-                           const uint8_t* mask, const uint32_t* first, float* xyz, float* color, float* opacity,
-                           float* uncertainty, float* scaling, float* rot, hipStream_t stream)
-{
-    if (N <= 0) return hipSuccess;
-    // persistent waves: 2 per SIMD (one workgroup of 8 per CU), each walks ~6 groups of 16 anchors at 200k anchors
-    const int emit_grid = GSD_MLP_GRID;
-    const int nb = ((N + 15) / 16 + GSD_EMIT_THREADS / 64 - 1) / (GSD_EMIT_THREADS / 64);
-    hipLaunchKernelGGL(gsd_emit_kernel, dim3(nb < emit_grid ? nb : emit_grid), dim3(GSD_EMIT_THREADS), 0, stream, N, K,
-                       gsd_pack(weights), vis, vis_count, feat, anchor, offsets, gscale, campos, neural_opacity, mask, first, xyz, color,
-                       opacity, uncertainty, scaling, rot);
-    return hipGetLastError();
-}
-
-hipError_t gsd_launch_backward(int N, int K, const float* const* weights, const int32_t* vis, const float* feat, const float* anchor,
-                                     const float* offsets, const float* gscale, const float* campos, const uint8_t* mask,
-                                     const uint32_t* first, const float* g_xyz, const float* g_color, const float* g_opacity,
-                                     const float* g_unc, const float* g_scaling, const float* g_rot, float* d_feat,
-                                     float* d_anchor, float* d_offsets, float* d_gscale, void* workspace, float* const* grads16,
-                                     hipStream_t stream)
+static hipError_t gsd_launch_backward(int N, int K, const float* const* weights, const int32_t* vis, const float* feat, const float* anchor,
+                                            const float* offsets, const float* gscale, const float* campos, const uint8_t* mask,
+                                            const uint32_t* first, const float* g_xyz, const float* g_color, const float* g_opacity,
+                                            const float* g_unc, const float* g_scaling, const float* g_rot, float* d_feat,
+                                            float* d_anchor, float* d_offsets, float* d_gscale, void* workspace, float* const* grads16,
+                                            hipStream_t stream)
 {
     GsdGrads G;
     for (int i = 0; i < 16; i++) G.g[i] = grads16[i];
@@ -1002,8 +974,6 @@ hipError_t gsd_launch_backward(int N, int K, const float* const* weights, const 
     return hipGetLastError();
 }
 
-size_t gsd_weight_grad_workspace_bytes() { return (size_t)GSD_WG_BLOCKS * (GSD_WG2_ROWS * GSD_WG2_COLS + GSD_WG1_ROWS * GSD_WG1_COLS) * sizeof(float); }
-
 // Gradient rows of the anchors a decode did NOT touch (hidden by the visibility mask): exact zeros, as the reference's
 // x[visible_mask] indexing leaves them.  One thread per model row; the visible rows are written by the backward kernel, so
 // the caller needs no model-sized zero-fill (57 MB per iteration at 200k anchors; typically a tenth of the rows are hidden).
@@ -1018,14 +988,6 @@ __global__ void __launch_bounds__(256) gsd_zero_hidden_kernel(int N, int K, cons
     for (int i = 0; i < 3; i++) d_anchor[(size_t)r * 3 + i] = 0.f;
     for (int i = 0; i < 3 * K; i++) d_off[(size_t)r * 3 * K + i] = 0.f;
     for (int i = 0; i < 6; i++) d_gs[(size_t)r * 6 + i] = 0.f;
-}
-
-hipError_t gsd_launch_zero_hidden(int N, int K, const uint8_t* visible_mask, float* d_feat, float* d_anchor, float* d_off, float* d_gs,
-                                  hipStream_t stream)
-{
-    if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gsd_zero_hidden_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, K, visible_mask, d_feat, d_anchor, d_off, d_gs);
-    return hipGetLastError();
 }
 
 // ---- visible-row list on the device (replaces torch.nonzero(visible_mask) and its host round trip) ------------------
@@ -1048,12 +1010,108 @@ __global__ void __launch_bounds__(256) gsd_rows_place_kernel(int N, const uint8_
     if (v) rows[block_base[blockIdx.x] + rank] = n;
 }
 
-hipError_t gsd_launch_visible_rows(int N, const uint8_t* visible_mask, int32_t* rows, uint32_t* count, uint32_t* block_scratch, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int gsr_check_decode(int N, int K, const float* const* weights)
 {
-    if (N <= 0) return hipMemsetAsync(count, 0, 4, stream);
+    if (N < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: N must be >= 0 (got %d)", N);
+    if (K < 1 || K > 10) return gsr_fail(GSR_ERR_UNSUPPORTED, "decode: n_offsets must be in 1..10 (got %d)", K);
+    if (!weights) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: weights is NULL");
+    for (int i = 0; i < 16; i++)
+        if (!weights[i]) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: weights[%d] is NULL", i);
+    return GSR_OK;
+}
+
+extern "C" int gsr_decode_visible_rows(int N, const uint8_t* visible_mask, int32_t* rows, uint32_t* count, uint32_t* block_scratch, void* stream_)
+{
+    if (N < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: N must be >= 0 (got %d)", N);
+    if (!count || (N > 0 && (!visible_mask || !rows || !block_scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N == 0) { GSR_HIP(hipMemsetAsync(count, 0, 4, stream), "decode visible rows"); return GSR_OK; }
     const int nb = (N + 255) / 256;
     hipLaunchKernelGGL(gsd_rows_count_kernel, dim3(nb), dim3(256), 0, stream, N, visible_mask, block_scratch);
     hipLaunchKernelGGL(gsd_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, block_scratch, count);
     hipLaunchKernelGGL(gsd_rows_place_kernel, dim3(nb), dim3(256), 0, stream, N, visible_mask, block_scratch, rows);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "decode visible rows");
+    return GSR_OK;
+}
+
+extern "C" int gsr_decode_count(int N, int K, const float* const* weights, const int32_t* visible, const uint32_t* visible_count, const float* feat, const float* anchor,
+                                const float* campos, float* neural_opacity, uint8_t* mask, uint8_t* count, uint32_t* first,
+                                uint32_t* total, uint32_t* block_scratch, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = gsr_check_decode(N, K, weights);
+    if (rc) return rc;
+    if (!total) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: total is NULL");
+    if (N == 0) { GSR_HIP(hipMemsetAsync(total, 0, 4, stream), "decode total"); return GSR_OK; }
+    if (!feat || !anchor || !campos || !neural_opacity || !mask || !count || !first || !block_scratch)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: a required pointer is NULL");
+    if (visible_count && !visible) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: visible_count without a row list");
+    const int nb = (N + GSD_THREADS - 1) / GSD_THREADS;
+    hipLaunchKernelGGL(gsd_count_kernel, dim3(nb < 8 * GSD_MLP_GRID ? nb : 8 * GSD_MLP_GRID), dim3(GSD_THREADS), 0, stream, N, K, gsd_pack(weights), visible, visible_count, feat, anchor, campos,
+                       neural_opacity, mask, count, block_scratch);
+    hipLaunchKernelGGL(gsd_scan_kernel, dim3(1), dim3(1024), 0, stream, nb, block_scratch, total);
+    hipLaunchKernelGGL(gsd_first_kernel, dim3(nb), dim3(GSD_THREADS), 0, stream, N, count, block_scratch, first);
+    GSR_HIP(hipGetLastError(), "decode count");
+    return GSR_OK;
+}
+
+extern "C" int gsr_decode_emit(int N, int K, const float* const* weights, const int32_t* visible, const uint32_t* visible_count, const float* feat, const float* anchor,
+                               const float* offsets, const float* grid_scaling, const float* campos,
+                               const float* neural_opacity, const uint8_t* mask, const uint32_t* first, float* xyz, float* color, float* opacity, float* uncertainty,
+                               float* scaling, float* rot, void* stream)
+{
+    int rc = gsr_check_decode(N, K, weights);
+    if (rc) return rc;
+    if (N == 0) return GSR_OK;
+    if (!feat || !anchor || !offsets || !grid_scaling || !campos || !neural_opacity || !mask || !first)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: a required pointer is NULL");
+    // persistent waves: 2 per SIMD (one workgroup of 8 per CU), each walks ~6 groups of 16 anchors at 200k anchors
+    const int emit_grid = GSD_MLP_GRID;
+    const int nb = ((N + 15) / 16 + GSD_EMIT_THREADS / 64 - 1) / (GSD_EMIT_THREADS / 64);
+    hipLaunchKernelGGL(gsd_emit_kernel, dim3(nb < emit_grid ? nb : emit_grid), dim3(GSD_EMIT_THREADS), 0, (hipStream_t)stream, N, K,
+                       gsd_pack(weights), visible, visible_count, feat, anchor, offsets, grid_scaling, campos, neural_opacity, mask, first, xyz, color,
+                       opacity, uncertainty, scaling, rot);
+    GSR_HIP(hipGetLastError(), "decode emit");
+    return GSR_OK;
+}
+
+extern "C" int gsr_decode_backward(int N, int K, const float* const* weights, const int32_t* visible, const float* feat,
+                                   const float* anchor, const float* offsets, const float* grid_scaling, const float* campos,
+                                         const uint8_t* mask, const uint32_t* first, const float* g_xyz, const float* g_color,
+                                         const float* g_opacity, const float* g_uncertainty, const float* g_scaling,
+                                         const float* g_rot, float* d_feat, float* d_anchor, float* d_offsets,
+                                         float* d_grid_scaling, void* workspace, float* const* grads16, void* stream)
+{
+    int rc = gsr_check_decode(N, K, weights);
+    if (rc) return rc;
+    if (!workspace || !grads16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: workspace / grads16 is NULL");
+    for (int i = 0; i < 16; i++)
+        if (!grads16[i]) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: grads16[%d] is NULL", i);
+    if (N > 0 && (!feat || !anchor || !offsets || !grid_scaling || !campos || !mask || !first || !d_feat || !d_anchor || !d_offsets ||
+                  !d_grid_scaling))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: a required pointer is NULL");
+    if (!campos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: campos is NULL");
+    GSR_HIP(gsd_launch_backward(N, K, weights, visible, feat, anchor, offsets, grid_scaling, campos, mask, first, g_xyz, g_color,
+                                      g_opacity, g_uncertainty, g_scaling, g_rot, d_feat, d_anchor, d_offsets, d_grid_scaling,
+                                      workspace, grads16, (hipStream_t)stream), "decode backward");
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_decode_weight_grad_workspace_bytes(void)
+{
+    return (size_t)GSD_WG_BLOCKS * (GSD_WG2_ROWS * GSD_WG2_COLS + GSD_WG1_ROWS * GSD_WG1_COLS) * sizeof(float);
+}
+
+extern "C" int gsr_decode_zero_hidden_rows(int N, int K, const uint8_t* visible_mask, float* d_feat, float* d_anchor, float* d_offsets,
+                                           float* d_grid_scaling, void* stream)
+{
+    if (N < 0 || K < 1 || K > 10) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: bad sizes N=%d K=%d", N, K);
+    if (N == 0) return GSR_OK;
+    if (!visible_mask || !d_feat || !d_anchor || !d_offsets || !d_grid_scaling)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "decode: a required pointer is NULL");
+    hipLaunchKernelGGL(gsd_zero_hidden_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, K, visible_mask, d_feat, d_anchor, d_offsets,
+                       d_grid_scaling);
+    GSR_HIP(hipGetLastError(), "decode zero hidden rows");
+    return GSR_OK;
 }

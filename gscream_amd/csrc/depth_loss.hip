@@ -15,7 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 
 #define GDL_THREADS 256
@@ -240,12 +241,17 @@ static GdlWorkspace gdl_carve(void* base, int H, int W)
     w.bytes = c.total();
     return w;
 }
-size_t gdl_workspace_bytes(int H, int W) { return gdl_carve(nullptr, H, W).bytes; }
 
-hipError_t gdl_launch_forward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
-                              const float* l1_weight, const float* grad_mask, float lambda_l1, float lambda_smooth,
-                              void* workspace, float* out5, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_depth_loss_workspace_bytes(int H, int W) { return gdl_carve(nullptr, H, W).bytes; }
+
+extern "C" int gsr_depth_loss_forward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
+                                      const float* l1_weight, const float* grad_mask, float lambda_l1, float lambda_smooth,
+                                      void* workspace, float* out5, void* stream_)
 {
+    if (H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth loss: bad size %dx%d", W, H);
+    if (!depth || !target || !workspace || !out5) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth loss: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
     const GdlWorkspace w = gdl_carve(workspace, H, W);
     const int N = H * W;
     int nb = (N + GDL_THREADS - 1) / GDL_THREADS;
@@ -254,15 +260,19 @@ hipError_t gdl_launch_forward(int H, int W, const float* depth, const float* tar
     hipLaunchKernelGGL(gdl_stencil_kernel, dim3(nb), dim3(GDL_THREADS), 0, stream, H, W, depth, target, l1_weight, grad_mask,
                        nb, w.part1, lambda_l1, lambda_smooth, w.params, w.G, w.part2);
     hipLaunchKernelGGL(gdl_finish_kernel, dim3(1), dim3(GDL_THREADS), 0, stream, nb, H, W, w.part2, lambda_l1, w.params, out5);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "depth loss forward");
+    return GSR_OK;
 }
 
-hipError_t gdl_launch_backward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
-                               const void* workspace, const float* upstream, float* dL_ddepth, hipStream_t stream)
+extern "C" int gsr_depth_loss_backward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
+                                       const void* workspace, const float* upstream, float* dL_ddepth, void* stream)
 {
+    if (H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth loss: bad size %dx%d", W, H);
+    if (!depth || !target || !workspace || !dL_ddepth) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth loss: a required pointer is NULL");
     const GdlWorkspace w = gdl_carve(const_cast<void*>(workspace), H, W);
     const int N = H * W;
-    hipLaunchKernelGGL(gdl_backward_kernel, dim3((N + GDL_THREADS - 1) / GDL_THREADS), dim3(GDL_THREADS), 0, stream, N, depth,
+    hipLaunchKernelGGL(gdl_backward_kernel, dim3((N + GDL_THREADS - 1) / GDL_THREADS), dim3(GDL_THREADS), 0, (hipStream_t)stream, N, depth,
                        target, lsq_mask, w.params, w.G, upstream, dL_ddepth);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "depth loss backward");
+    return GSR_OK;
 }

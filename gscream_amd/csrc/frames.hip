@@ -23,12 +23,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
 
 #define FRM_THREADS 256
+// Stats: one workgroup per FRAME_STATS_CHUNK elements of a frame writes eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}: the
+// workspace is B*chunks*8 doubles, used again by the second pass (lo2 / hi2).
+#define FRAME_STATS_CHUNK 4096
 static_assert(FRAME_STATS_CHUNK % FRM_THREADS == 0, "every thread of a full chunk reads the same number of elements");
 static_assert(sizeof(gsr_frame_panel) == 72, "gsr_frame_panel is 3 pointers, 4 strides and 3 ints (padded to 8 bytes)");
 
@@ -155,29 +159,6 @@ static FrmStatsWork frm_stats_carve(void* base, int B, int H, int W)
     const int chunks = (int)(((size_t)H * (size_t)W + FRAME_STATS_CHUNK - 1) / FRAME_STATS_CHUNK);
     double* partials = c.take<double>((size_t)B * (size_t)chunks * 8, sizeof(double));
     return { partials, chunks, c.total() };
-}
-size_t frames_stats_workspace_bytes(int B, int H, int W) { return frm_stats_carve(nullptr, B, H, W).bytes; }
-
-hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
-                               double* stats, float* params, hipStream_t stream)
-{
-    const int HW = H * W;  // < 2^29
-    const FrmStatsWork w = frm_stats_carve(workspace, B, H, W);
-    const int chunks = w.chunks;
-    double* const partials = w.partials;
-    const dim3 grid((uint32_t)chunks, (uint32_t)B);
-    hipLaunchKernelGGL(frame_stats_partial_kernel<1>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, lsq_mask, (const float*)nullptr, partials);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(frame_stats_finish_kernel<1>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
-    e = hipGetLastError();
-    if (e != hipSuccess || !target) return e;
-    hipLaunchKernelGGL(frame_stats_partial_kernel<2>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, (const float*)nullptr, (const float*)params,
-                       partials);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(frame_stats_finish_kernel<2>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
-    return hipGetLastError();
 }
 
 // ---- compose ----
@@ -308,9 +289,85 @@ __global__ void __launch_bounds__(FRM_THREADS) frame_compose_kernel(int H, int W
     }
 }
 
-hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
-                                 uint8_t* out, bool dwords, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int frames_check_sizes(const char* what, int B, int H, int W)
 {
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: B=%d H=%d W=%d (need all > 0)", what, B, H, W);
+    if (B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: B=%d has too many frames (need B <= 65535)", what, B);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL / 4)  // (H*W*4 itself can pass 2^63)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d has too many pixels (need H*W*4 < 2^31 - 256)", what, H, W);
+    // (no accepted size wraps the carve: 65535 frames of fewer than 2^17 chunks, 64 bytes each)
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_frame_stats_workspace_bytes(int B, int H, int W)
+{
+    if (frames_check_sizes("frame stats", B, H, W)) return 0;
+    return frm_stats_carve(nullptr, B, H, W).bytes;
+}
+
+extern "C" int gsr_frame_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
+                               double* stats, float* params, void* stream_)
+{
+    if (int rc = frames_check_sizes("frame stats", B, H, W)) return rc;
+    if (!depth || !workspace || !stats || !params)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame stats: depth, workspace, stats or params is NULL");
+    if (lsq_mask && !target) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame stats: an lsq_mask needs a target, which is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int HW = H * W;  // < 2^29
+    const FrmStatsWork w = frm_stats_carve(workspace, B, H, W);
+    const int chunks = w.chunks;
+    double* const partials = w.partials;
+    const dim3 grid((uint32_t)chunks, (uint32_t)B);
+    hipLaunchKernelGGL(frame_stats_partial_kernel<1>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, lsq_mask, (const float*)nullptr, partials);
+    GSR_HIP(hipGetLastError(), "frame stats");
+    hipLaunchKernelGGL(frame_stats_finish_kernel<1>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
+    GSR_HIP(hipGetLastError(), "frame stats");
+    if (!target) return GSR_OK;
+    hipLaunchKernelGGL(frame_stats_partial_kernel<2>, grid, dim3(FRM_THREADS), 0, stream, HW, depth, target, (const float*)nullptr, (const float*)params,
+                       partials);
+    GSR_HIP(hipGetLastError(), "frame stats");
+    hipLaunchKernelGGL(frame_stats_finish_kernel<2>, dim3((uint32_t)B), dim3(FRM_THREADS), 0, stream, chunks, (const double*)partials, stats, params);
+    GSR_HIP(hipGetLastError(), "frame stats");
+    return GSR_OK;
+}
+
+extern "C" int gsr_frame_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
+                                 uint8_t* out, void* stream_)
+{
+    if (int rc = frames_check_sizes("frame compose", B, H, W_out)) return rc;
+    if (channels_out != 3 && channels_out != 4)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: channels_out=%d (need 3 or 4)", channels_out);
+    if (n < 1 || n > GSR_FRAME_MAX_PANELS)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: n=%d panels (need 1 .. %d)", n, GSR_FRAME_MAX_PANELS);
+    if (!panels || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panels or out is NULL");
+    int order[GSR_FRAME_MAX_PANELS];
+    for (int j = 0; j < n; j++) {
+        const gsr_frame_panel& p = panels[j];
+        if (p.mode < GSR_FRAME_QUANT || p.mode > GSR_FRAME_CMAP_MPL)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has the unknown mode %d", j, p.mode);
+        if (!p.src) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has a NULL src", j);
+        if (p.mode == GSR_FRAME_ABSDIFF && !p.src2) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d is ABSDIFF with a NULL src2", j);
+        if (p.mode >= GSR_FRAME_CMAP_CV && (!p.lut || !params))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d has a CMAP mode with a NULL lut or params", j);
+        if (p.width <= 0 || p.x0 < 0 || (int64_t)p.x0 + (int64_t)p.width > (int64_t)W_out)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d covers columns [%d, %lld), outside [0, %d) or empty", j, p.x0,
+                            (long long)p.x0 + (long long)p.width, W_out);
+        int k = j;  // insertion by x0
+        for (; k > 0 && panels[order[k - 1]].x0 > p.x0; k--) order[k] = order[k - 1];
+        order[k] = j;
+    }
+    int next = 0;
+    for (int k = 0; k < n; k++) {
+        const gsr_frame_panel& p = panels[order[k]];
+        if (p.x0 != next)
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: panel %d starts at column %d where %d is next (the panels %s)", order[k], p.x0,
+                            next, p.x0 < next ? "overlap" : "leave a gap");
+        next = p.x0 + p.width;
+    }
+    if (next != W_out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "frame compose: the panels end at column %d of %d (they leave a gap)", next, W_out);
+    const bool dwords = ((uintptr_t)out & 3) == 0 && (channels_out == 4 || W_out % 4 == 0);
+    hipStream_t stream = (hipStream_t)stream_;
     FrmTable tab = {};
     for (int j = 0; j < n; j++) tab.p[j] = panels[j];
     tab.n = n;
@@ -323,5 +380,6 @@ hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int 
         if (dwords) hipLaunchKernelGGL((frame_compose_kernel<3, true>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
         else hipLaunchKernelGGL((frame_compose_kernel<3, false>), grid, block, 0, stream, H, W_out, quads, tab, params, out);
     }
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "frame compose");
+    return GSR_OK;
 }

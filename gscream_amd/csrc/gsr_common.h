@@ -1,4 +1,5 @@
-// gsr_common.h -- internal layout of the workspaces shared by all translation units.
+// gsr_common.h -- internal layout of the rasterizer's workspaces and its launchers, shared by the rasterizer's translation units
+// (api, preprocess, binning, blend, gauss_bwd; knn.hip borrows the tile sort).  The other modules keep their layouts in their own files.
 //
 // HBM layout (P Gaussians, T = gx*gy 16x16 tiles, N = W*H pixels, R instances):
 //
@@ -37,7 +38,6 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/gsraster.h"
-#include "../../include/gsraster_jpeg_decode.h"
 #include "gsr_carve.h"
 
 #define GSR_TILE 16
@@ -402,192 +402,3 @@ hipError_t gsr_launch_gauss_backward(int P, int D, int M, const GsrCam& cam, con
                                      float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dfeatures,
                                      float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                                      float* dL_drotations, hipStream_t stream);
-
-// ---- loss.hip ----
-size_t gsl_workspace_bytes(int C, int H, int W);
-hipError_t gsl_launch_forward(int C, int H, int W, const float* img, const float* gt, const float* weight, float a_l1,
-                              float a_ssim, void* workspace, float* out, int keep_state, int window_size, hipStream_t stream);
-hipError_t gsl_launch_backward(int C, int H, int W, const float* img, const float* gt, const float* weight, float a_l1,
-                               float a_ssim, const void* workspace, const float* upstream, float* dL_dimg,
-                               int window_size, hipStream_t stream);
-
-// ---- knn.hip ----
-size_t gsk_workspace_bytes(int P);
-hipError_t gsk_launch(int P, const float* points, float* mean_dist2, void* workspace, hipStream_t stream, const char** why);
-
-// ---- decode.hip ----
-hipError_t gsd_launch_count(int N, int K, const float* const* weights, const int32_t* vis, const uint32_t* vis_count, const float* feat, const float* anchor,
-                            const float* campos, float* neural_opacity, uint8_t* mask, uint8_t* count, uint32_t* first,
-                            uint32_t* total, uint32_t* block_scratch, hipStream_t stream);
-hipError_t gsd_launch_emit(int N, int K, const float* const* weights, const int32_t* vis, const uint32_t* vis_count, const float* feat, const float* anchor,
-                           const float* offsets, const float* gscale, const float* campos, const float* neural_opacity,
-                           const uint8_t* mask, const uint32_t* first, float* xyz, float* color, float* opacity,
-                           float* uncertainty, float* scaling, float* rot, hipStream_t stream);
-hipError_t gsd_launch_visible_rows(int N, const uint8_t* visible_mask, int32_t* rows, uint32_t* count, uint32_t* block_scratch, hipStream_t stream);
-hipError_t gsd_launch_zero_hidden(int N, int K, const uint8_t* visible_mask, float* d_feat, float* d_anchor, float* d_off, float* d_gs,
-                                  hipStream_t stream);
-hipError_t gsd_launch_backward(int N, int K, const float* const* weights, const int32_t* vis, const float* feat, const float* anchor,
-                                     const float* offsets, const float* gscale, const float* campos, const uint8_t* mask,
-                                     const uint32_t* first, const float* g_xyz, const float* g_color, const float* g_opacity,
-                                     const float* g_unc, const float* g_scaling, const float* g_rot, float* d_feat,
-                                     float* d_anchor, float* d_offsets, float* d_gscale, void* workspace, float* const* grads16,
-                                     hipStream_t stream);
-size_t gsd_weight_grad_workspace_bytes();
-
-// ---- depth_loss.hip (depth terms) ----
-size_t gdl_workspace_bytes(int H, int W);
-hipError_t gdl_launch_forward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
-                              const float* l1_weight, const float* grad_mask, float lambda_l1, float lambda_smooth,
-                              void* workspace, float* out5, hipStream_t stream);
-hipError_t gdl_launch_backward(int H, int W, const float* depth, const float* target, const float* lsq_mask,
-                               const void* workspace, const float* upstream, float* dL_ddepth, hipStream_t stream);
-
-// ---- stats.hip (densification statistics) ----
-hipError_t gst_launch_training_stats(int Nv, int K, int M, const int32_t* visible, const float* neural_opacity,
-                                     const uint8_t* selection, const uint32_t* first, const uint8_t* update_filter,
-                                     const float* viewspace_grad, float* opacity_accum, float* anchor_demon,
-                                     float* offset_gradient_accum, float* offset_denom, hipStream_t stream);
-
-// ---- anchor_grow.hip (anchor growing: one level's dedupe + max; torch_scatter.scatter_max) ----
-size_t gag_workspace_bytes(int N, int L);
-hipError_t gag_launch_keys(int N, int K, int L, const float* anchor, const float* offset, const float* scaling, const uint8_t* mask, float inv,
-                           void* workspace, int64_t* keys, int32_t* rows, int32_t* info, hipStream_t stream);
-hipError_t gag_launch_emit(int N, int K, int F, int L, int M, const float* feat, const int64_t* sorted_keys, const int64_t* perm,
-                           const int32_t* rows, float cur_size, void* workspace, float* candidate_anchor, float* new_feat, int32_t* info,
-                           hipStream_t stream);
-hipError_t gag_launch_scatter_max(int R, int F, int S, const float* src, const int64_t* index, float* out, int64_t* argmax, hipStream_t stream);
-
-// ---- crossattn.hip (the attention core of BidirectionalCrossAttention: both softmax directions, forward and backward) ----
-size_t gca_workspace_bytes(int B, int H, int I, int J);
-hipError_t gca_launch_forward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
-                              const uint8_t* mask, const uint8_t* cmask, float scale, float* out, float* cout, void* workspace,
-                              hipStream_t stream);
-hipError_t gca_launch_backward(int B, int H, int I, int J, const float* qk, const float* v, const float* cqk, const float* cv,
-                               const uint8_t* mask, const uint8_t* cmask, float scale, const float* out, const float* cout,
-                               const float* d_out, const float* d_cout, void* workspace, float* d_qk, float* d_v, float* d_cqk,
-                               float* d_cv, hipStream_t stream);
-
-// ---- anchor_sample.hip (the cross-attention anchor sampler of train.py:436-511: classify, count, keyed radix select, ordered compaction) ----
-size_t gas_workspace_bytes(int N, int max_pairs);
-hipError_t gas_launch(int N, int H, int W, const uint8_t* visible, const float* px, const float* py, const float* gt_mask, int min_y,
-                      int max_y, int min_x, int max_x, int max_pairs, uint64_t seed, void* workspace, uint8_t* src_mask, uint8_t* dst_mask,
-                      int64_t* src_rows, int64_t* dst_rows, int32_t* info, hipStream_t stream);
-
-// ---- anchor_adjust.hip (GaussianModel.adjust_anchor / prune_anchor: offset statistics, prune plan, one table-driven row gather) ----
-size_t gaa_workspace_bytes(int N);
-hipError_t gaa_launch_offsets(int L0, const float* accum, const float* denom, float thr_half, float* grads_norm, uint8_t* offset_mask,
-                              hipStream_t stream);
-hipError_t gaa_launch_plan(int N, const float* opacity_accum, const float* anchor_demon, const uint8_t* prune_mask, float min_opacity, float thr,
-                           void* workspace, int32_t* keep_rows, uint8_t* reset, int32_t* info, hipStream_t stream);
-hipError_t gaa_launch_gather(int n_keep, int n_copies, const gsr_adjust_copy* copies, const int32_t* keep_rows, const uint8_t* offset_mask,
-                             int L0, const uint8_t* reset, hipStream_t stream);
-
-// ---- scene_init.hip (voxelize_sample / create_from_pcd: 64-bit key sort, voxel dedupe, k-th smallest, initial state; validated by the caller) ----
-size_t gsi_sort_workspace_bytes(int N);
-hipError_t gsi_sort_launch(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, hipStream_t stream);
-size_t gsi_voxelize_workspace_bytes(int N);
-hipError_t gsi_voxelize_launch(int N, int fp64, const void* points, double v_host, const float* v_dev, void* workspace, void* out,
-                               int32_t* info, hipStream_t stream);
-size_t gsi_kth_workspace_bytes(int N);
-hipError_t gsi_kth_launch(int N, int k, const float* values, void* workspace, float* out, hipStream_t stream);
-hipError_t gsi_fill_launch(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
-                           float* feat, float* rotation, float* opac, float* unc, float* radii, float* xyz_max, hipStream_t stream);
-
-// adam.hip: one launch for all tensors (validated by the caller; tensors with n == 0 are skipped)
-hipError_t adam_launch(int n_tensors, const gsr_adam_tensor* tensors, hipStream_t stream);
-
-// normals.hip: depth -> point map, point map -> per-pixel plane-fit normals (both validated by the caller)
-hipError_t normals_launch_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, hipStream_t stream);
-hipError_t normals_launch_fit(int H, int W, const float* points, int size, float gamma, double eps, float* normals, hipStream_t stream);
-
-// metrics.hip: per-image L1 / MSE / PSNR / 5x5 reflect-padded SSIM, plain and masked (validated by the caller).  One workgroup per
-// 16 x 32 tile of a plane writes eight fp64 partial sums: the workspace is B*C*tiles*8 doubles.
-size_t metrics_workspace_bytes(int B, int C, int H, int W);
-hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
-                          long long mask_stride_c, int flags, const double taps[3] /* g_0, g_1, g_2 of the window */, void* workspace,
-                          double* sums, float* metrics, hipStream_t stream);
-
-// lpips.hip: conv3x3 + bias + ReLU on the f32 matrix cores and the LPIPS chain (validated by the caller).  The packed weights of a layer
-// are [Cout / LPIPS_CONV_NB][ceil(Cin / LPIPS_CONV_KC)][9][LPIPS_CONV_KC][LPIPS_CONV_NB] floats, zero where the channel is beyond Cin.
-#define LPIPS_CONV_KC 8
-#define LPIPS_CONV_NB 64
-hipError_t lpips_launch_conv(int N, int Cin, int Cout, int H, int W, const float* in, const float* wpack, const float* bias, float* out, int flags,
-                             hipStream_t stream);
-size_t lpips_workspace_bytes(int B, int H, int W);
-hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
-                        const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
-                        float* out_layers, float* out_masked, float* out_spatial, hipStream_t stream);
-
-// frames.hip: render_set's output frames (validated by the caller).  Stats: one workgroup per FRAME_STATS_CHUNK elements of a frame writes
-// eight doubles {a00, a01, a11, b0, b1, lo, hi, NaN count}: the workspace is B*chunks*8 doubles, used again by the second pass (lo2 / hi2).
-// Compose: `dwords` = whole-dword stores (the caller has checked out's alignment and channels_out == 4 or W_out % 4 == 0).
-#define FRAME_STATS_CHUNK 4096
-size_t frames_stats_workspace_bytes(int B, int H, int W);
-hipError_t frames_launch_stats(int B, int H, int W, const float* depth, const float* target, const float* lsq_mask, void* workspace,
-                               double* stats, float* params, hipStream_t stream);
-hipError_t frames_launch_compose(int B, int H, int W_out, int channels_out, int n, const gsr_frame_panel* panels, const float* params,
-                                 uint8_t* out, bool dwords, hipStream_t stream);
-
-// png.hip: uint8 pictures -> PNG files (validated by the caller).  The workspace holds, per picture, the filtered stream, the rows' Adler-32
-// partials (two words each), the chunks' byte counts and one slot of PNG_SLOT_BYTES per chunk (the chunk's deflate bytes).
-#define PNG_SLOT_BYTES (GSR_PNG_CHUNK + 32)
-struct PngLayout {
-    size_t row_bytes, stream_bytes, chunks;             // 1 + W*C, H * row_bytes, ceil(stream_bytes / GSR_PNG_CHUNK)
-    size_t adler_off, sizes_off, slots_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
-    size_t capacity;                                    // what a file can take at most (every chunk stored)
-};
-PngLayout png_layout(int H, int W, int C);
-hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
-                             uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream);
-
-// jpeg.hip: uint8 pictures -> baseline JPEG files (validated by the caller).  The workspace holds, per picture, the quantised
-// coefficients (int16 [blocks][64], zigzag order, blocks in scan order), then the intervals' byte counts / file offsets, then one
-// word that says whether the file fits.
-#define JPEG_FILE_HEADER_MAX 640
-struct JpegLayout {
-    int comps, mcu, bpm;                  // components; MCU edge in pixels (8 or 16); blocks per MCU (1, 3, 6)
-    int mcux, mcuy;                       // MCUs per row and per column
-    int ri;                               // MCUs per restart interval (the resolved value)
-    size_t mcus, blocks, intervals;       // per picture
-    size_t file_header;                   // bytes in front of the scan: 629 (C = 3) or 334 (C = 1)
-    size_t sizes_off, fits_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
-    size_t capacity;                      // file_header + 416 blocks + 3 mcus + 2
-};
-struct JpegTables {                       // travels in the kernel arguments
-    uint8_t quant[2][64];                 // natural order, scaled to the quality
-    uint8_t header[JPEG_FILE_HEADER_MAX]; // SOI .. SOS
-};
-JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interval);
-void jpeg_fill_tables(JpegTables* t, int H, int W, int C, int quality, int subsampling, const JpegLayout& lay);
-hipError_t jpeg_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C,
-                              const JpegTables& tables, const JpegLayout& lay, uint8_t* out, size_t out_stride, void* workspace,
-                              hipStream_t stream);
-
-// png_decode.hip: PNG files -> uint8 pictures (pointers and counts validated by the caller; the tables are checked on the device).
-// The workspace holds the files' inflated streams, then per piece {size, flag, offset} of the segment that starts there, then per
-// file the Adler-32 of its trailer.
-size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces);
-size_t pd_tables_bytes(int nfiles, int npieces);  // the tables' part alone: the least workspace a call is taken with
-hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
-                             int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
-                             hipStream_t stream);
-
-// jpeg_decode.hip: baseline JPEG files -> uint8 pictures (pointers and counts validated by the caller; the tables are checked on the
-// device).  The workspace holds the caller's area (the files' coefficients and component planes), then per restart interval {start, end,
-// status, owner}.
-size_t jpeg_decode_workspace_bytes(size_t area_bytes, int nintervals);
-size_t jd_tables_bytes(int nintervals);  // the tables' part alone: the least workspace a call is taken with
-hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
-                              const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
-                              size_t workspace_bytes, hipStream_t stream);
-
-// resize.hip: PIL's Image.resize, one pass (or one NEAREST gather) per launch (validated by the caller)
-hipError_t resize_launch_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis,
-                            int out_len, const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride,
-                            long long out_row_stride, int epilogue, hipStream_t stream);
-hipError_t resize_launch_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
-                             const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride,
-                             long long out_row_stride, hipStream_t stream);
-hipError_t resize_launch_nearest(const void* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int is_f32,
-                                 int H_out, int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
-                                 long long out_row_stride, int epilogue, hipStream_t stream);

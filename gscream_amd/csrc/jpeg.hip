@@ -21,7 +21,8 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 #include "jpeg_tables.h"
 
@@ -33,13 +34,30 @@
 #define JPEG_BLOCK_BYTES 416  // 22 + 63 * 26 bits = 208 bytes, doubled by stuffing
 static_assert(GSR_JPEG_INTERVAL_BLOCKS == 1024, "the entropy kernel has at most 1024 threads, one per block of an interval");
 
+#define JPEG_FILE_HEADER_MAX 640
+struct JpegLayout {
+    int comps, mcu, bpm;                  // components; MCU edge in pixels (8 or 16); blocks per MCU (1, 3, 6)
+    int mcux, mcuy;                       // MCUs per row and per column
+    int ri;                               // MCUs per restart interval (the resolved value)
+    size_t mcus, blocks, intervals;       // per picture
+    size_t file_header;                   // bytes in front of the scan: 629 (C = 3) or 334 (C = 1)
+    size_t sizes_off, fits_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
+    size_t capacity;                      // file_header + 416 blocks + 3 mcus + 2
+};
+struct JpegTables {                       // travels in the kernel arguments
+    uint8_t quant[2][64];                 // natural order, scaled to the quality
+    uint8_t header[JPEG_FILE_HEADER_MAX]; // SOI .. SOS
+};
+
 __constant__ int jpeg_dct[64] = { JPEG_DCT_ROWS };
 __constant__ uint8_t jpeg_zigzag[64] = { JPEG_ZIGZAG_LIST };
 __constant__ uint32_t jpeg_dc_codes[2][12] = { { JPEG_DC0_CODES }, { JPEG_DC1_CODES } };     // code | length << 16
 __constant__ uint32_t jpeg_ac_codes[2][256] = { { JPEG_AC0_CODES }, { JPEG_AC1_CODES } };
 
 // ---- layout, tables and the file header (host) ----
-JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interval)
+// The workspace holds, per picture, the quantised coefficients (int16 [blocks][64], zigzag order, blocks in scan order), then the
+// intervals' byte counts / file offsets, then one word that says whether the file fits.
+static JpegLayout jpeg_layout(int H, int W, int C, int subsampling, int restart_interval)
 {
     JpegLayout l;
     l.comps = C;
@@ -77,7 +95,7 @@ static uint8_t* jpeg_put_dht(uint8_t* p, int id, const uint8_t* bits, const uint
     memcpy(p + 16, values, (size_t)n);
     return p + 16 + n;
 }
-void jpeg_fill_tables(JpegTables* t, int H, int W, int C, int quality, int subsampling, const JpegLayout& lay)
+static void jpeg_fill_tables(JpegTables* t, int H, int W, int C, int quality, int subsampling, const JpegLayout& lay)
 {
     memset(t, 0, sizeof(*t));
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
@@ -411,18 +429,78 @@ static hipError_t jpeg_launch_entropy(uint8_t* ws, const JpegLayout& lay, int B,
     return hipGetLastError();
 }
 
-hipError_t jpeg_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C,
-                              const JpegTables& tables, const JpegLayout& lay, uint8_t* out, size_t out_stride, void* workspace,
-                              hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int jpeg_check_sizes(int B, int H, int W, int C, int subsampling)
 {
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: B=%d H=%d W=%d (need all > 0)", B, H, W);
+    if (C != 1 && C != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: C=%d (need 1 or 3)", C);
+    if (B > 65535 || H > 65535 || W > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: B=%d H=%d W=%d (need all <= 65535)", B, H, W);
+    if (subsampling != 444 && subsampling != 420) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: subsampling=%d (need 444 or 420)", subsampling);
+    if (subsampling == 420 && C == 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: subsampling 420 with C=1 (a grey picture has no chroma)");
+    if (jpeg_layout(H, W, C, subsampling, 0).capacity >= ((size_t)1 << 31))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: H=%d W=%d C=%d has a capacity of 2^31 bytes or more", H, W, C);
+    // (no accepted size wraps the layout: a picture's part is below 2^32 bytes, B below 2^16)
+    return GSR_OK;
+}
+
+static int jpeg_check_interval(int C, int subsampling, int restart_interval)
+{
+    const int most = GSR_JPEG_INTERVAL_BLOCKS / (C == 1 ? 1 : (subsampling == 420 ? 6 : 3));
+    if (restart_interval < 0 || restart_interval > most)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: restart_interval=%d (need 0 = the default, or 1 .. %d MCUs)", restart_interval, most);
+    return GSR_OK;
+}
+
+// a pointer the kernels may use: device memory of this process
+static bool jpeg_on_device(const void* p)
+{
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer: the error is ours to clear)
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice;
+}
+
+extern "C" size_t gsr_jpeg_capacity(int H, int W, int C, int subsampling)
+{
+    return jpeg_check_sizes(1, H, W, C, subsampling) ? 0 : jpeg_layout(H, W, C, subsampling, 0).capacity;
+}
+
+extern "C" size_t gsr_jpeg_workspace_bytes(int B, int H, int W, int C, int subsampling, int restart_interval)
+{
+    if (jpeg_check_sizes(B, H, W, C, subsampling) || jpeg_check_interval(C, subsampling, restart_interval)) return 0;
+    return (size_t)B * jpeg_layout(H, W, C, subsampling, restart_interval).per_picture;
+}
+
+extern "C" int gsr_jpeg_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int quality,
+                               int subsampling, int restart_interval, uint8_t* out, size_t out_stride, void* workspace, void* stream_)
+{
+    if (int rc = jpeg_check_sizes(B, H, W, C, subsampling)) return rc;
+    if (int rc = jpeg_check_interval(C, subsampling, restart_interval)) return rc;
+    if (!images || !out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: images, out or workspace is NULL");
+    if (quality < 1 || quality > 100) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: quality=%d (need 1 .. 100)", quality);
+    if (row_stride < (long long)W * C) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: row_stride=%lld is below W*C=%lld", row_stride, (long long)W * C);
+    if (B > 1 && image_stride < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: image_stride=%lld is negative", image_stride);
+    const JpegLayout lay = jpeg_layout(H, W, C, subsampling, restart_interval);
+    const size_t need = GSR_JPEG_HEADER_BYTES + lay.file_header;
+    if (out_stride < need || out_stride % 4 || ((uintptr_t)out & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: out_stride=%zu (need >= %zu = the four words + the file header, a multiple of 4) or out is not 4-byte aligned",
+                        out_stride, need);
+    if ((uintptr_t)workspace & 15) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: workspace is not 16-byte aligned");
+    if (!jpeg_on_device(images) || !jpeg_on_device(out) || !jpeg_on_device(workspace))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg: images, out or workspace is not device memory");
+    JpegTables tables;
+    jpeg_fill_tables(&tables, H, W, C, quality, subsampling, lay);
+    hipStream_t stream = (hipStream_t)stream_;
     uint8_t* ws = (uint8_t*)workspace;
     const size_t groups = (lay.blocks + JPEG_TR_BLOCKS - 1) / JPEG_TR_BLOCKS;
     hipLaunchKernelGGL(jpeg_transform_kernel, dim3((uint32_t)groups, (uint32_t)B), dim3(JPEG_TR_THREADS), 0, stream, images, row_stride, image_stride, H, W,
                        C, tables, lay, ws);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    GSR_HIP(hipGetLastError(), "jpeg encode");
     const int most = lay.ri * lay.bpm;  // blocks of a full interval: the workgroup's size
-    if (most <= 64) return jpeg_launch_entropy<64>(ws, lay, B, out, out_stride, tables, stream);
-    if (most <= 256) return jpeg_launch_entropy<256>(ws, lay, B, out, out_stride, tables, stream);
-    return jpeg_launch_entropy<1024>(ws, lay, B, out, out_stride, tables, stream);
+    if (most <= 64) GSR_HIP(jpeg_launch_entropy<64>(ws, lay, B, out, out_stride, tables, stream), "jpeg encode");
+    else if (most <= 256) GSR_HIP(jpeg_launch_entropy<256>(ws, lay, B, out, out_stride, tables, stream), "jpeg encode");
+    else GSR_HIP(jpeg_launch_entropy<1024>(ws, lay, B, out, out_stride, tables, stream), "jpeg encode");
+    return GSR_OK;
 }

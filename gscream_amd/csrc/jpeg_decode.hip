@@ -23,7 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 #include "jpeg_entropy.h"
 
@@ -63,8 +64,7 @@ static JdCarve jd_carve(void* base, size_t area_bytes, int nintervals)
     r.bytes = c.total();
     return r;
 }
-size_t jd_tables_bytes(int nintervals) { return jd_carve(nullptr, 0, nintervals).bytes; }
-size_t jpeg_decode_workspace_bytes(size_t area_bytes, int nintervals) { return jd_carve(nullptr, area_bytes, nintervals).bytes; }
+static size_t jd_tables_bytes(int nintervals) { return jd_carve(nullptr, 0, nintervals).bytes; }  // the tables' part alone: the least workspace a call is taken with
 
 // what the sizes and the sampling of a file make
 struct JdGeometry {
@@ -425,9 +425,9 @@ __global__ void __launch_bounds__(256) jpeg_decode_colour_kernel(const gsr_jpeg_
     }
 }
 
-hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
-                              const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
-                              size_t workspace_bytes, hipStream_t stream)
+static hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
+                                     const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
+                                     size_t workspace_bytes, hipStream_t stream)
 {
     const size_t tables = jd_tables_bytes(nintervals);
     if (workspace_bytes < tables) return hipErrorInvalidValue;
@@ -450,4 +450,40 @@ hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpe
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(jpeg_decode_colour_kernel, dim3(g_colour, (uint32_t)nfiles), dim3(256), 0, stream, files, (JdWorkspace)ws, out, (const int32_t*)status);
     return hipGetLastError();
+}
+
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_jpeg_decode_workspace_bytes(size_t area_bytes, int nfiles, int nintervals)
+{
+    if (nfiles <= 0 || nintervals <= 0 || area_bytes >= ((size_t)1 << 40)) return 0;  // (no accepted size wraps the carve: 2^40 + 2^31 * 16)
+    return jd_carve(nullptr, area_bytes, nintervals).bytes;
+}
+
+extern "C" int gsr_jpeg_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant,
+                               int nquant, const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status,
+                               void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!bytes || !files || !quant || !huffman || !out || !status || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: bytes, files, quant, huffman, out, status or workspace is NULL");
+    if (nfiles <= 0 || nintervals <= 0 || nquant <= 0 || nhuffman <= 0 || nfiles > 65535)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: nfiles=%d nintervals=%d nquant=%d nhuffman=%d (need all > 0, nfiles <= 65535)", nfiles,
+                        nintervals, nquant, nhuffman);
+    if (nbytes >= ((size_t)1 << 32) || out_bytes >= ((size_t)1 << 32))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: nbytes=%zu out_bytes=%zu (need both < 2^32)", nbytes, out_bytes);
+    if (((uintptr_t)bytes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)quant & 15) || ((uintptr_t)files & 7) ||
+        ((uintptr_t)status & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: bytes, out, workspace and quant are 16-byte aligned, files 8, status 4");
+    if (workspace_bytes < jd_tables_bytes(nintervals))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
+    GSR_HIP(jpeg_launch_decode(bytes, nbytes, files, nfiles, nintervals, quant, nquant, huffman, nhuffman, out, out_bytes, status, workspace,
+                               workspace_bytes, (hipStream_t)stream),
+            "jpeg decode");
+    return GSR_OK;
+}
+
+extern "C" const char* gsr_jpeg_decode_status_name(int code)
+{
+    static const char* const names[] = {"ok", "truncated", "bit pattern with no symbol", "invalid symbol", "run past coefficient 63",
+                                        "restart markers miscounted, misnumbered or misplaced", "table entry out of bounds"};
+    return code >= GSR_JPEG_DECODE_OK && code <= GSR_JPEG_DECODE_TABLE ? names[code] : "?";
 }

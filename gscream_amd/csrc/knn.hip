@@ -26,6 +26,9 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "gsr_api.h"
+#include "gsr_carve.h"
+#include "gsr_common.h"  // GsrFrame, gsr_launch_tile_sort: the buckets are sorted by the rasterizer's tile sort
 #include "gsr_reduce.h"
 #include "gsr_scan.h"
 
@@ -280,17 +283,19 @@ static GskWorkspace gsk_carve(void* base, int P)
     return w;
 }
 
-size_t gsk_workspace_bytes(int P) { return gsk_carve(nullptr, P).bytes; }
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_knn_workspace_bytes(int P) { return gsk_carve(nullptr, P).bytes; }
 
-hipError_t gsk_launch(int P, const float* points, float* mean_dist2, void* workspace, hipStream_t stream, const char** why)
+extern "C" int gsr_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream_)
 {
-    *why = "";
-    if (P <= 0) return hipSuccess;
+    if (P < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "knn: P must be >= 0 (got %d)", P);
+    if (P == 0) return GSR_OK;
+    if (!points || !mean_dist2 || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "knn: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
     const GskWorkspace w = gsk_carve(workspace, P);
     const int nb256 = (P + 255) / 256, nparts = nb256 < GSK_MINMAX_BLOCKS ? nb256 : GSK_MINMAX_BLOCKS;
     hipLaunchKernelGGL(gsk_minmax_kernel, dim3(nparts), dim3(256), 0, stream, P, points, w.part);
-    hipError_t e = hipMemsetAsync(w.bucket_count, 0, (size_t)GSK_BUCKETS * 4, stream);
-    if (e != hipSuccess) return e;
+    GSR_HIP(hipMemsetAsync(w.bucket_count, 0, (size_t)GSK_BUCKETS * 4, stream), "knn");
     hipLaunchKernelGGL(gsk_morton_kernel, dim3(nb256), dim3(256), 0, stream, P, nparts, points, w.part, w.codes, w.bucket_count);
     hipLaunchKernelGGL(gsk_bucket_scan_kernel, dim3(1), dim3(1024), 0, stream, w.bucket_count, w.ranges, w.cursor);
     hipLaunchKernelGGL(gsk_bucket_scatter_kernel, dim3(nb256), dim3(256), 0, stream, P, w.codes, w.cursor, w.seg_keys);
@@ -303,8 +308,7 @@ hipError_t gsk_launch(int P, const float* points, float* mean_dist2, void* works
         f.bin.seg_keys = w.seg_keys;
         f.bin.point_list = w.ids_sorted;
         f.stream = stream;
-        e = gsr_launch_tile_sort(f, -1, 0 /* complete sorts */, false, true /* no written-slot flags */);
-        if (e != hipSuccess) { *why = "bucket sort"; return e; }
+        GSR_HIP(gsr_launch_tile_sort(f, -1, 0 /* complete sorts */, false, true /* no written-slot flags */), "knn");
     }
     const int nboxes = (P + GSK_BOX - 1) / GSK_BOX;
     hipLaunchKernelGGL(gsk_gather_kernel, dim3(nb256), dim3(256), 0, stream, P, points, w.ids_sorted, w.sp);
@@ -312,5 +316,6 @@ hipError_t gsk_launch(int P, const float* points, float* mean_dist2, void* works
     hipLaunchKernelGGL(gsk_superbox_kernel, dim3((nboxes + GSK_BOX - 1) / GSK_BOX), dim3(GSK_BOX), 0, stream, nboxes, w.boxes, w.sboxes);
     hipLaunchKernelGGL(gsk_search_kernel, dim3((P + GSK_GROUP - 1) / GSK_GROUP), dim3(GSK_GROUP), 0, stream, P, nboxes, w.sp,
                        w.boxes, w.sboxes, mean_dist2);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "knn");
+    return GSR_OK;
 }

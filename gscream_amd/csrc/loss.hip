@@ -21,7 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 
 #define GSL_TW 32
@@ -272,8 +273,6 @@ static GslWorkspace gsl_carve(void* base, int C, int H, int W)
     return w;
 }
 
-size_t gsl_workspace_bytes(int C, int H, int W) { return gsl_carve(nullptr, C, H, W).bytes; }
-
 // taps of create_window(window_size) (loss_utils.py:113-121) centred in the 11-tap frame; window_size odd, 1..11
 static bool gsl_make_taps(int window_size, GslTaps& t)
 {
@@ -293,11 +292,37 @@ static bool gsl_make_taps(int window_size, GslTaps& t)
     return true;
 }
 
-hipError_t gsl_launch_forward(int C, int H, int W, const float* img, const float* gt, const float* weight, float a_l1,
-                              float a_ssim, void* workspace, float* out, int keep_state, int window_size, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_loss_workspace_bytes(int C, int H, int W) { return gsl_carve(nullptr, C, H, W).bytes; }
+
+static int gsr_check_loss_args(int C, int H, int W, const float* img, const float* gt, const void* workspace)
 {
+    if (C < 1 || H < 1 || W < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: C, H, W must be >= 1 (got %d, %d, %d)", C, H, W);
+    if ((long long)C * H * W > 0x7fffffffLL) return gsr_fail(GSR_ERR_UNSUPPORTED, "loss: image too large");
+    // (no accepted size wraps the carve: three planes of C*H*W floats, below 2^35 bytes)
+    if (!img || !gt || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: a required pointer is NULL");
+    return GSR_OK;
+}
+
+static int gsr_check_window(int window_size)
+{
+    if (window_size < 1 || window_size > 11 || (window_size & 1) == 0)
+        return gsr_fail(GSR_ERR_UNSUPPORTED, "loss: window_size must be odd and in 1..11 (got %d)", window_size);
+    return GSR_OK;
+}
+
+extern "C" int gsr_rgb_loss_forward_window(int C, int H, int W, const float* img, const float* gt, const float* weight,
+                                           float a_l1, float a_ssim, int window_size, void* workspace, float* out3, int keep_state,
+                                           void* stream_)
+{
+    int rc = gsr_check_loss_args(C, H, W, img, gt, workspace);
+    if (rc) return rc;
+    rc = gsr_check_window(window_size);
+    if (rc) return rc;
+    if (!out3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: out3 is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
     GslTaps taps;
-    if (!gsl_make_taps(window_size, taps)) return hipErrorInvalidValue;
+    gsl_make_taps(window_size, taps);  // (gsr_check_window has passed: it makes them)
     const GslWorkspace w = gsl_carve(workspace, C, H, W);
     const dim3 grid(w.gx, w.gy, C);
     if (keep_state)
@@ -307,19 +332,39 @@ hipError_t gsl_launch_forward(int C, int H, int W, const float* img, const float
         hipLaunchKernelGGL(gsl_forward_kernel<false>, grid, dim3(256), 0, stream, H, W, img, gt, weight, w.d_mu1, w.d_e11,
                            w.d_e12, w.partial, taps);
     hipLaunchKernelGGL(gsl_finish_kernel, dim3(1), dim3(256), 0, stream, w.gx * w.gy * C, w.partial,
-                       (double)C * (double)H * (double)W, a_l1, a_ssim, out);
-    return hipGetLastError();
+                       (double)C * (double)H * (double)W, a_l1, a_ssim, out3);
+    GSR_HIP(hipGetLastError(), "rgb loss forward");
+    return GSR_OK;
 }
 
-hipError_t gsl_launch_backward(int C, int H, int W, const float* img, const float* gt, const float* weight, float a_l1,
-                               float a_ssim, const void* workspace, const float* upstream, float* dL_dimg,
-                               int window_size, hipStream_t stream)
+extern "C" int gsr_rgb_loss_backward_window(int C, int H, int W, const float* img, const float* gt, const float* weight,
+                                            float a_l1, float a_ssim, int window_size, const void* workspace,
+                                            const float* upstream, float* dL_dimg, void* stream)
 {
+    int rc = gsr_check_loss_args(C, H, W, img, gt, workspace);
+    if (rc) return rc;
+    rc = gsr_check_window(window_size);
+    if (rc) return rc;
+    if (!dL_dimg) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "loss: dL_dimg is NULL");
     GslTaps taps;
-    if (!gsl_make_taps(window_size, taps)) return hipErrorInvalidValue;
+    gsl_make_taps(window_size, taps);  // (gsr_check_window has passed: it makes them)
     const GslWorkspace w = gsl_carve(const_cast<void*>(workspace), C, H, W);
     const double count = (double)C * (double)H * (double)W;
-    hipLaunchKernelGGL(gsl_backward_kernel, dim3(w.gx, w.gy, C), dim3(256), 0, stream, H, W, img, gt, weight, w.d_mu1,
+    hipLaunchKernelGGL(gsl_backward_kernel, dim3(w.gx, w.gy, C), dim3(256), 0, (hipStream_t)stream, H, W, img, gt, weight, w.d_mu1,
                        w.d_e11, w.d_e12, (float)((double)a_l1 / count), (float)((double)a_ssim / count), upstream, dL_dimg, taps);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "rgb loss backward");
+    return GSR_OK;
+}
+
+extern "C" int gsr_rgb_loss_forward(int C, int H, int W, const float* img, const float* gt, const float* weight,
+                                    float a_l1, float a_ssim, void* workspace, float* out3, int keep_state, void* stream)
+{
+    return gsr_rgb_loss_forward_window(C, H, W, img, gt, weight, a_l1, a_ssim, 11, workspace, out3, keep_state, stream);
+}
+
+extern "C" int gsr_rgb_loss_backward(int C, int H, int W, const float* img, const float* gt, const float* weight,
+                                     float a_l1, float a_ssim, const void* workspace, const float* upstream,
+                                     float* dL_dimg, void* stream)
+{
+    return gsr_rgb_loss_backward_window(C, H, W, img, gt, weight, a_l1, a_ssim, 11, workspace, upstream, dL_dimg, stream);
 }

@@ -26,7 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
@@ -38,6 +39,10 @@ typedef float lp_v4 __attribute__((ext_vector_type(4)));
 #define LPC_THREADS 256
 #define LPC_TW 32
 #define LPC_TH 8
+// The packed weights of a layer are [Cout / LPIPS_CONV_NB][ceil(Cin / LPIPS_CONV_KC)][9][LPIPS_CONV_KC][LPIPS_CONV_NB] floats, zero where
+// the channel is beyond Cin.
+#define LPIPS_CONV_KC 8
+#define LPIPS_CONV_NB 64
 #define LPC_KC LPIPS_CONV_KC            // input channels per staged chunk
 #define LPC_NB LPIPS_CONV_NB            // output channels per workgroup
 #define LPC_HW (LPC_TW + 2)             // 34 staged columns
@@ -304,8 +309,8 @@ static const int lp_tap_channels[5] = {64, 128, 256, 512, 512};
 static size_t lp_packed_floats(int Cin, int Cout) { return (size_t)(Cout / LPC_NB) * (size_t)((Cin + LPC_KC - 1) / LPC_KC) * LPC_WCHUNK; }
 static int lp_blocks(long long hw) { return (int)((hw + LP_THREADS - 1) / LP_THREADS); }
 
-hipError_t lpips_launch_conv(int N, int Cin, int Cout, int H, int W, const float* in, const float* wpack, const float* bias, float* out, int flags,
-                             hipStream_t stream)
+static hipError_t lpips_launch_conv(int N, int Cin, int Cout, int H, int W, const float* in, const float* wpack, const float* bias, float* out, int flags,
+                                    hipStream_t stream)
 {
     const int tiles_x = (W + LPC_TW - 1) / LPC_TW, tiles_y = (H + LPC_TH - 1) / LPC_TH;
     hipLaunchKernelGGL(lpips_conv_kernel, dim3((uint32_t)(tiles_x * tiles_y), (uint32_t)(Cout / LPC_NB), (uint32_t)N), dim3(LPC_THREADS), 0, stream,
@@ -343,11 +348,9 @@ static lp_carve lp_plan(void* base, int B, int H, int W)
     return p;
 }
 
-size_t lpips_workspace_bytes(int B, int H, int W) { return lp_plan(nullptr, B, H, W).total; }
-
-hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
-                        const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
-                        float* out_layers, float* out_masked, float* out_spatial, hipStream_t stream)
+static hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
+                               const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
+                               float* out_layers, float* out_masked, float* out_spatial, hipStream_t stream)
 {
     const lp_carve c = lp_plan(workspace, B, H, W);
     float* cur = c.buf[0];  // holds the newest activations
@@ -405,4 +408,52 @@ hipError_t lpips_launch(int B, int H, int W, const float* in0, const float* in1,
     fa.sblocks = c.sblocks;
     hipLaunchKernelGGL(lpips_finish_kernel, dim3((uint32_t)B), dim3(LP_THREADS), 0, stream, fa, out_plain, out_layers, out_masked);
     return hipGetLastError();
+}
+
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int lpips_check_sizes(int B, int H, int W)
+{
+    if (B <= 0 || B > 32767) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: B=%d (need 1 .. 32767 views: 2B images are one batch)", B);
+    if (H < 16 || W < 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d (need both >= 16: four 2x2 pools)", H, W);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: H=%d W=%d has too many pixels (need H*W < 2^31 - 256)", H, W);
+    // (no accepted size wraps the carve: an activation buffer is 2 B * 64 * H*W floats < 2^15 * 2^9 * 2^31 = 2^55 bytes)
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_lpips_workspace_bytes(int B, int H, int W)
+{
+    if (lpips_check_sizes(B, H, W)) return 0;
+    return lp_plan(nullptr, B, H, W).total;
+}
+
+extern "C" int gsr_lpips(int B, int H, int W, const float* in0, const float* in1, int flags, const float* conv_weights, const float* conv_bias,
+                         const float* lin_weights, const uint8_t* mask, long long mask_stride_b, void* workspace, float* out_plain,
+                         float* out_layers, float* out_masked, float* out_spatial, void* stream)
+{
+    if (int rc = lpips_check_sizes(B, H, W)) return rc;
+    if (!in0 || !in1 || !conv_weights || !conv_bias || !lin_weights || !workspace || !out_plain)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: in0, in1, conv_weights, conv_bias, lin_weights, workspace or out_plain is NULL");
+    if (flags & ~GSR_LPIPS_NORMALIZE) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: unknown flag bits in %d", flags);
+    if (mask_stride_b < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "lpips: negative mask stride %lld", mask_stride_b);
+    GSR_HIP(lpips_launch(B, H, W, in0, in1, flags, conv_weights, conv_bias, lin_weights, mask, mask_stride_b, workspace, out_plain, out_layers,
+                         out_masked, out_spatial, (hipStream_t)stream),
+            "lpips");
+    return GSR_OK;
+}
+
+extern "C" int gsr_conv3x3_relu(int B, int Cin, int Cout, int H, int W, const float* in, const float* weights_packed, const float* bias,
+                                float* out, int flags, void* stream)
+{
+    if (B <= 0 || B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: B=%d (need 1 .. 65535 images)", B);
+    if (Cin <= 0 || Cout <= 0 || Cout % LPIPS_CONV_NB != 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: Cin=%d Cout=%d (need Cin > 0 and Cout a positive multiple of %d)", Cin, Cout, LPIPS_CONV_NB);
+    if (Cin > 65536 || Cout > 65536) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: Cin=%d Cout=%d is too wide", Cin, Cout);
+    if (H <= 0 || W <= 0 || (int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: H=%d W=%d (need both > 0 and H*W < 2^31 - 256)", H, W);
+    if (!in || !weights_packed || !bias || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: in, weights_packed, bias or out is NULL");
+    if (flags & ~(GSR_LPIPS_NORMALIZE | GSR_LPIPS_SCALING)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: unknown flag bits in %d", flags);
+    if (flags && Cin != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "conv3x3: the input transforms are for Cin = 3 (got %d)", Cin);
+    GSR_HIP(lpips_launch_conv(B, Cin, Cout, H, W, in, weights_packed, bias, out, flags, (hipStream_t)stream), "conv3x3");
+    return GSR_OK;
 }

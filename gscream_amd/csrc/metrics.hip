@@ -29,7 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 
 #pragma clang fp contract(off)
@@ -189,19 +190,47 @@ static MetWork met_carve(void* base, int B, int C, int H, int W)
     double* partials = c.take<double>((size_t)B * (size_t)C * (size_t)tiles_x * (size_t)tiles_y * 8, sizeof(double));
     return { partials, tiles_x, tiles_x * tiles_y, c.total() };
 }
-size_t metrics_workspace_bytes(int B, int C, int H, int W) { return met_carve(nullptr, B, C, H, W).bytes; }
 
-hipError_t metrics_launch(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
-                          long long mask_stride_c, int flags, const double taps[3], void* workspace, double* sums, float* metrics,
-                          hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int metrics_check_sizes(int B, int C, int H, int W)
 {
+    if (B <= 0 || C <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: B=%d C=%d (need both > 0)", B, C);
+    if ((int64_t)B * (int64_t)C > 65535)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: B=%d C=%d has too many planes (need B*C <= 65535)", B, C);
+    if (H < 3 || W < 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: H=%d W=%d (need both >= 3: reflect padding of 2)", H, W);
+    if ((double)C * (double)H * (double)W >= 2147483392.0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: C=%d H=%d W=%d has too many elements (need C*H*W < 2^31 - 256)", C, H, W);
+    // (no accepted size wraps the carve: 65535 planes of fewer than 2^22 tiles, 64 bytes each)
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_image_metrics_workspace_bytes(int B, int C, int H, int W)
+{
+    if (metrics_check_sizes(B, C, H, W)) return 0;
+    return met_carve(nullptr, B, C, H, W).bytes;
+}
+
+extern "C" int gsr_image_metrics(int B, int C, int H, int W, const float* pred, const float* gt, const uint8_t* mask, long long mask_stride_b,
+                                 long long mask_stride_c, int flags, void* workspace, double* sums, float* metrics, void* stream_)
+{
+    if (int rc = metrics_check_sizes(B, C, H, W)) return rc;
+    if (!pred || !gt || !workspace || !sums || !metrics)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: pred, gt, workspace, sums or metrics is NULL");
+    if (flags & ~(GSR_METRICS_CLAMP | GSR_METRICS_QUANTIZE)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: unknown flag bits in %d", flags);
+    if (mask_stride_b < 0 || mask_stride_c < 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image metrics: negative mask stride (%lld, %lld)", mask_stride_b, mask_stride_c);
+    double taps[3], total = 0.0;  // g_k = exp(-(k-2)^2 / 4.5) / sum, k = 0 .. 4 (sigma 1.5), in fp64
+    for (int k = 0; k < 3; k++) taps[k] = exp(-(double)((k - 2) * (k - 2)) / 4.5);
+    total = ((taps[0] + taps[1]) + taps[2]) + (taps[1] + taps[0]);
+    for (int k = 0; k < 3; k++) taps[k] /= total;
+    hipStream_t stream = (hipStream_t)stream_;
     const MetWork w = met_carve(workspace, B, C, H, W);
     const int tiles_x = w.tiles_x, tiles = w.tiles;
     met_taps t = {taps[0], taps[1], taps[2]};
     hipLaunchKernelGGL(metrics_tile_kernel, dim3((uint32_t)tiles, (uint32_t)(B * C)), dim3(MET_THREADS), 0, stream, H, W, C, tiles_x, pred, gt,
                        mask, mask_stride_b, mask_stride_c, flags, t, w.partials);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    GSR_HIP(hipGetLastError(), "image metrics");
     hipLaunchKernelGGL(metrics_finish_kernel, dim3((uint32_t)B), dim3(MET_THREADS), 0, stream, C * tiles, (const double*)w.partials, sums, metrics);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "image metrics");
+    return GSR_OK;
 }

@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
 
 // The exact fp32 operations are functions of this file below `#pragma clang fp contract(off)`, as in adam.hip: nrm_sub / nrm_mul /
 // nrm_add / nrm_div are __fsub_rn / __fmul_rn / __fadd_rn / __fdiv_rn in meaning.  The toolchain's own are plain operators in a header
@@ -139,18 +139,35 @@ __global__ void __launch_bounds__(NRM_THREADS) point_normals_kernel(int H, int W
     out[2] = (float)-(vz != vz ? 0.0 : vz);
 }
 
-hipError_t normals_launch_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int normals_check_frame(const char* what, int H, int W)
 {
-    const uint32_t n = (uint32_t)H * (uint32_t)W;
-    hipLaunchKernelGGL(depth_points_kernel, dim3((n + NRM_THREADS - 1u) / NRM_THREADS), dim3(NRM_THREADS), 0, stream, H, W, depth, K, c2w,
-                       points);
-    return hipGetLastError();
+    if (H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d (need both > 0)", what, H, W);
+    if ((int64_t)H * (int64_t)W >= 0x7fffff00LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d has too many pixels (need H*W < 2^31 - 256)", what, H, W);
+    return GSR_OK;
 }
 
-hipError_t normals_launch_fit(int H, int W, const float* points, int size, float gamma, double eps, float* normals, hipStream_t stream)
+extern "C" int gsr_depth_points(int H, int W, const float* depth, const float* K, const float* c2w, float* points, void* stream)
 {
+    if (int rc = normals_check_frame("depth points", H, W)) return rc;
+    if (!depth || !K || !c2w || !points) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "depth points: depth, K, c2w or points is NULL");
+    const uint32_t n = (uint32_t)H * (uint32_t)W;
+    hipLaunchKernelGGL(depth_points_kernel, dim3((n + NRM_THREADS - 1u) / NRM_THREADS), dim3(NRM_THREADS), 0, (hipStream_t)stream, H, W, depth, K, c2w,
+                       points);
+    GSR_HIP(hipGetLastError(), "depth points");
+    return GSR_OK;
+}
+
+extern "C" int gsr_point_normals(int H, int W, const float* points, int size, float gamma, double eps, float* normals, void* stream)
+{
+    if (int rc = normals_check_frame("point normals", H, W)) return rc;
+    if (size < 1 || size > 15 || size % 2 == 0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: size=%d (need an odd size, 1 .. 15)", size);
+    if (!points || !normals) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "point normals: points or normals is NULL");
     const int tiles_x = (W + NRM_TILE - 1) / NRM_TILE, tiles_y = (H + NRM_TILE - 1) / NRM_TILE;  // tiles_x * tiles_y <= 2^27 + 2^24
-    hipLaunchKernelGGL(point_normals_kernel, dim3((uint32_t)tiles_x * (uint32_t)tiles_y), dim3(NRM_THREADS), 0, stream, H, W, tiles_x, points,
+    hipLaunchKernelGGL(point_normals_kernel, dim3((uint32_t)tiles_x * (uint32_t)tiles_y), dim3(NRM_THREADS), 0, (hipStream_t)stream, H, W, tiles_x, points,
                        size, gamma, eps, normals);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "point normals");
+    return GSR_OK;
 }

@@ -22,7 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_scan.h"
 #include "png_crc.h"
 
@@ -33,11 +34,19 @@
 #define PNG_PER (PNG_CHUNK / PNG_DEF_THREADS)  // bytes of a chunk a deflate thread owns
 #define PNG_ADLER 65521u
 #define PNG_LITLEN 286
+#define PNG_SLOT_BYTES (GSR_PNG_CHUNK + 32)
 static_assert(PNG_PER == 32, "a thread's run heads are one 32-bit mask, and at most one 258-byte match starts in its span");
 static_assert(PNG_SLOT_BYTES >= PNG_CHUNK + 2 + 5 + 5 + 4 && PNG_SLOT_BYTES % 16 == 0, "zlib header, stored header, marker, one dword of slack");
 
 // ---- layout of the workspace (per picture; every part a multiple of 16 bytes) ----
-PngLayout png_layout(int H, int W, int C)
+// The workspace holds, per picture, the filtered stream, the rows' Adler-32 partials (two words each), the chunks' byte counts and one
+// slot of PNG_SLOT_BYTES per chunk (the chunk's deflate bytes).
+struct PngLayout {
+    size_t row_bytes, stream_bytes, chunks;             // 1 + W*C, H * row_bytes, ceil(stream_bytes / GSR_PNG_CHUNK)
+    size_t adler_off, sizes_off, slots_off, per_picture;  // byte offsets inside a picture's part of the workspace, and its size
+    size_t capacity;                                    // what a file can take at most (every chunk stored)
+};
+static PngLayout png_layout(int H, int W, int C)
 {
     PngLayout l;
     l.row_bytes = 1 + (size_t)W * (size_t)C;
@@ -644,8 +653,8 @@ __global__ void __launch_bounds__(PNG_ASM_THREADS) png_assemble_kernel(int H, in
     }
 }
 
-hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
-                             uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream)
+static hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
+                                    uint8_t* out, size_t out_stride, void* workspace, hipStream_t stream)
 {
     const PngLayout lay = png_layout(H, W, C);
     const size_t lds = PNG_CHUNK + PNG_SLOT_BYTES;  // beyond 64 KiB: a one-time opt-in per device
@@ -669,4 +678,42 @@ hipError_t png_launch_encode(const uint8_t* images, long long row_stride, long l
     hipLaunchKernelGGL(png_assemble_kernel, dim3((uint32_t)lay.chunks, (uint32_t)B), dim3(PNG_ASM_THREADS), 0, stream, H, W, C, (const uint8_t*)ws, lay, out,
                        out_stride);
     return hipGetLastError();
+}
+
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int png_check_sizes(int B, int H, int W, int C)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: B=%d H=%d W=%d (need all > 0)", B, H, W);
+    if (C != 1 && C != 3 && C != 4) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: C=%d (need 1, 3 or 4)", C);
+    if (B > 65535) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: B=%d has too many pictures (need B <= 65535)", B);
+    if ((int64_t)W * C >= (1 << 24)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: W=%d C=%d has too long a row (need W*C < 2^24)", W, C);
+    if ((int64_t)H * ((int64_t)W * C + 1) >= 0x70000000LL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: H=%d W=%d C=%d has too many bytes (need H*(1 + W*C) < 0x70000000)", H, W, C);
+    // (no accepted size wraps the layout: a picture's part is below 2^32 bytes, B below 2^16)
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_png_capacity(int H, int W, int C) { return png_check_sizes(1, H, W, C) ? 0 : png_layout(H, W, C).capacity; }
+
+extern "C" size_t gsr_png_workspace_bytes(int B, int H, int W, int C)
+{
+    return png_check_sizes(B, H, W, C) ? 0 : (size_t)B * png_layout(H, W, C).per_picture;
+}
+
+extern "C" int gsr_png_encode(const uint8_t* images, long long row_stride, long long image_stride, int B, int H, int W, int C, int filter,
+                              uint8_t* out, size_t out_stride, void* workspace, void* stream)
+{
+    if (int rc = png_check_sizes(B, H, W, C)) return rc;
+    if (!images || !out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: images, out or workspace is NULL");
+    if (filter < 0 || filter > GSR_PNG_FILTER_ADAPTIVE)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: filter=%d (need 0 .. 4 or GSR_PNG_FILTER_ADAPTIVE)", filter);
+    if (row_stride < (long long)W * C) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: row_stride=%lld is below W*C=%lld", row_stride, (long long)W * C);
+    if (B > 1 && image_stride < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: image_stride=%lld is negative", image_stride);
+    const size_t need = GSR_PNG_HEADER_BYTES + png_layout(H, W, C).capacity;
+    if (out_stride < need || out_stride % 4 || ((uintptr_t)out & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: out_stride=%zu (need >= %zu = header + capacity, a multiple of 4) or out is not 4-byte aligned",
+                        out_stride, need);
+    if ((uintptr_t)workspace & 15) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png: workspace is not 16-byte aligned");
+    GSR_HIP(png_launch_encode(images, row_stride, image_stride, B, H, W, C, filter, out, out_stride, workspace, (hipStream_t)stream), "png encode");
+    return GSR_OK;
 }

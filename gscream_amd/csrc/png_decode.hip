@@ -24,7 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 #include "png_crc.h"
 #include "png_inflate.h"
@@ -66,8 +67,7 @@ static PdCarve pd_carve(void* base, size_t stream_bytes, int nfiles, int npieces
     r.bytes = c.total();
     return r;
 }
-size_t pd_tables_bytes(int nfiles, int npieces) { return pd_carve(nullptr, 0, nfiles, npieces).bytes; }
-size_t png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces) { return pd_carve(nullptr, stream_bytes, nfiles, npieces).bytes; }
+static size_t pd_tables_bytes(int nfiles, int npieces) { return pd_carve(nullptr, 0, nfiles, npieces).bytes; }  // the tables' part alone: the least workspace a call is taken with
 
 struct PdTeam {
     int lane, lanes;
@@ -400,9 +400,9 @@ __global__ void __launch_bounds__(PD_CRC_THREADS) png_crc_kernel(const uint8_t* 
     }
 }
 
-hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
-                             int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
-                             hipStream_t stream)
+static hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
+                                    int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream)
 {
     const size_t tables = pd_tables_bytes(nfiles, npieces);
     if (workspace_bytes < tables) return hipErrorInvalidValue;
@@ -437,4 +437,30 @@ hipError_t png_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" size_t gsr_png_decode_workspace_bytes(size_t stream_bytes, int nfiles, int npieces)
+{
+    if (nfiles <= 0 || npieces <= 0 || stream_bytes >= ((size_t)1 << 40)) return 0;  // (no accepted size wraps the carve: 2^40 + 2^31 * 12 + 2^31 * 4)
+    return pd_carve(nullptr, stream_bytes, nfiles, npieces).bytes;
+}
+
+extern "C" int gsr_png_decode(const uint8_t* bytes, size_t nbytes, const gsr_png_file* files, int nfiles, const gsr_png_piece* pieces, int npieces,
+                              int verify_crc, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!bytes || !files || !pieces || !out || !status || !workspace)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: bytes, files, pieces, out, status or workspace is NULL");
+    if (nfiles <= 0 || npieces <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: nfiles=%d npieces=%d (need both > 0)", nfiles, npieces);
+    if (nbytes >= ((size_t)1 << 32) || out_bytes >= ((size_t)1 << 32))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: nbytes=%zu out_bytes=%zu (need both < 2^32)", nbytes, out_bytes);
+    if (((uintptr_t)bytes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)files & 7) || ((uintptr_t)pieces & 7) ||
+        ((uintptr_t)status & 3))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: bytes, out and workspace are 16-byte aligned, the tables 8, status 4");
+    if (workspace_bytes < pd_tables_bytes(nfiles, npieces))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "png decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
+    GSR_HIP(png_launch_decode(bytes, nbytes, files, nfiles, pieces, npieces, verify_crc, out, out_bytes, status, workspace, workspace_bytes,
+                              (hipStream_t)stream),
+            "png decode");
+    return GSR_OK;
 }

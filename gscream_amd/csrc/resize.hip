@@ -29,7 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
 
 #pragma clang fp contract(off)
 
@@ -267,18 +267,70 @@ __global__ void __launch_bounds__(RZ_THREADS) resize_nearest_f32_kernel(const fl
         p[(long long)blockIdx.z * src_image_stride + (long long)sy * src_row_stride + sx];
 }
 
-// ---- launchers (validated by the caller) -------------------------------------------------------------------------------------------
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
 static inline uint32_t rz_div_up(long long a, long long b) { return (uint32_t)((a + b - 1) / b); }
 
-hipError_t resize_launch_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis,
-                            int out_len, const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride,
-                            long long out_row_stride, int epilogue, hipStream_t stream)
+static hipError_t resize_launch_nearest(const void* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int is_f32,
+                                        int H_out, int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
+                                        long long out_row_stride, int epilogue, hipStream_t stream)
 {
+    const dim3 grid(rz_div_up(W_out, RZ_THREADS), (uint32_t)H_out, (uint32_t)n);
+    if (is_f32)
+        hipLaunchKernelGGL(resize_nearest_f32_kernel, grid, dim3(RZ_THREADS), 0, stream, (const float*)src, src_image_stride, src_row_stride, H, W,
+                           H_out, W_out, yidx, xidx, (float*)out, out_image_stride, out_row_stride);
+    else
+        hipLaunchKernelGGL(resize_nearest_u8_kernel, grid, dim3(RZ_THREADS), 0, stream, (const uint8_t*)src, src_image_stride, src_row_stride, H, W, C,
+                           H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride, epilogue);
+    return hipGetLastError();
+}
+
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+static int resize_check(const char* what, const void* src, const void* out, long long src_image_stride, long long src_row_stride, int n, int H, int W,
+                        int C, int H_out, int W_out, long long out_image_stride, long long out_row_stride, int epilogue)
+{
+    if (!src || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: src or out is NULL", what);
+    if (n < 1 || H < 1 || W < 1 || H_out < 1 || W_out < 1)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: n, H, W and the output sizes must be >= 1 (got %d, %d x %d -> %d x %d)", what, n, H, W, H_out, W_out);
+    if (C < 1 || C > 4) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: C=%d (need 1 .. 4)", what, C);
+    if (n > 65535 || H > 65535 || W > 65535 || H_out > 65535 || W_out > 65535)
+        return gsr_fail(GSR_ERR_UNSUPPORTED, "%s: n, H, W and the output sizes are at most 65535", what);
+    if (epilogue != GSR_RESIZE_U8 && epilogue != GSR_RESIZE_DIV255 && epilogue != GSR_RESIZE_GT0)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: epilogue=%d", what, epilogue);
+    if (src_row_stride < (long long)W * C || (n > 1 && src_image_stride < (long long)(H - 1) * src_row_stride + (long long)W * C))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: source strides %lld / %lld are below the row or the picture", what, src_image_stride, src_row_stride);
+    if (epilogue == GSR_RESIZE_U8) {
+        if (out_row_stride < (long long)W_out * C || (n > 1 && out_image_stride < (long long)(H_out - 1) * out_row_stride + (long long)W_out * C))
+            return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: output strides %lld / %lld are below the row or the picture", what, out_image_stride, out_row_stride);
+    } else if (out_row_stride != W_out || out_image_stride != (long long)C * H_out * W_out) {
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the float forms are contiguous [n][C][H'][W'] (strides %lld / %lld)", what, out_image_stride, out_row_stride);
+    }
+    return GSR_OK;
+}
+
+static int resize_check_pass(const char* what, int axis, int out_len, const void* bounds, const void* coeffs, int ksize)
+{
+    if (axis != GSR_RESIZE_HORIZONTAL && axis != GSR_RESIZE_VERTICAL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: axis=%d", what, axis);
+    if (!bounds || !coeffs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bounds or coeffs is NULL", what);
+    if (ksize < 1 || out_len < 1 || (long long)out_len * ksize > 0x7fffffffLL)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: ksize=%d, out_len=%d", what, ksize, out_len);
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int axis, int out_len,
+                             const int32_t* bounds, const int32_t* coeffs, int ksize, void* out, long long out_image_stride, long long out_row_stride,
+                             int epilogue, void* stream_)
+{
+    if (int rc = resize_check_pass("resize_u8", axis, out_len, bounds, coeffs, ksize)) return rc;
+    const int H_out = axis == GSR_RESIZE_VERTICAL ? out_len : H, W_out = axis == GSR_RESIZE_VERTICAL ? W : out_len;
+    if (int rc = resize_check("resize_u8", src, out, src_image_stride, src_row_stride, n, H, W, C, H_out, W_out, out_image_stride, out_row_stride, epilogue))
+        return rc;
+    hipStream_t stream = (hipStream_t)stream_;
     if (axis == GSR_RESIZE_VERTICAL) {
         hipLaunchKernelGGL(resize_v_u8_kernel, dim3(rz_div_up((long long)W * C, RZ_THREADS), (uint32_t)out_len, (uint32_t)n), dim3(RZ_THREADS), 0, stream,
                            src, src_image_stride, src_row_stride, H, W, C, out_len, bounds, coeffs, ksize, out, out_image_stride, out_row_stride,
                            epilogue);
-        return hipGetLastError();
+        GSR_HIP(hipGetLastError(), "resize_u8");
+        return GSR_OK;
     }
     const dim3 grid(rz_div_up(out_len, RZ_TILE), rz_div_up(H, RZ_ROWS * RZ_GROUPS), (uint32_t)n);
 #define RZ_LAUNCH_H(CH)                                                                                                                        \
@@ -291,13 +343,20 @@ hipError_t resize_launch_u8(const uint8_t* src, long long src_image_stride, long
     default: RZ_LAUNCH_H(4); break;
     }
 #undef RZ_LAUNCH_H
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "resize_u8");
+    return GSR_OK;
 }
 
-hipError_t resize_launch_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
-                             const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride,
-                             long long out_row_stride, hipStream_t stream)
+extern "C" int gsr_resize_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int axis, int out_len,
+                              const int32_t* bounds, const double* coeffs, int ksize, float* out, long long out_image_stride, long long out_row_stride,
+                              void* stream_)
 {
+    if (int rc = resize_check_pass("resize_f32", axis, out_len, bounds, coeffs, ksize)) return rc;
+    const int H_out = axis == GSR_RESIZE_VERTICAL ? out_len : H, W_out = axis == GSR_RESIZE_VERTICAL ? W : out_len;
+    if (int rc = resize_check("resize_f32", src, out, src_image_stride, src_row_stride, n, H, W, 1, H_out, W_out, out_image_stride, out_row_stride,
+                              GSR_RESIZE_U8))
+        return rc;
+    hipStream_t stream = (hipStream_t)stream_;
     if (axis == GSR_RESIZE_VERTICAL)
         hipLaunchKernelGGL(resize_v_f32_kernel, dim3(rz_div_up(W, RZ_THREADS), (uint32_t)out_len, (uint32_t)n), dim3(RZ_THREADS), 0, stream, src,
                            src_image_stride, src_row_stride, H, W, out_len, bounds, coeffs, ksize, out, out_image_stride, out_row_stride);
@@ -305,19 +364,34 @@ hipError_t resize_launch_f32(const float* src, long long src_image_stride, long 
         hipLaunchKernelGGL(resize_h_f32_kernel, dim3(rz_div_up(out_len, RZ_TILE), rz_div_up(H, RZ_ROWS * RZ_GROUPS), (uint32_t)n), dim3(RZ_THREADS), 0,
                            stream, src, src_image_stride, src_row_stride, H, W, out_len, bounds, coeffs, ksize, out, out_image_stride,
                            out_row_stride);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "resize_f32");
+    return GSR_OK;
 }
 
-hipError_t resize_launch_nearest(const void* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int is_f32,
-                                 int H_out, int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
-                                 long long out_row_stride, int epilogue, hipStream_t stream)
+extern "C" int gsr_resize_nearest_u8(const uint8_t* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int C, int H_out,
+                                     int W_out, const int32_t* yidx, const int32_t* xidx, void* out, long long out_image_stride,
+                                     long long out_row_stride, int epilogue, void* stream)
 {
-    const dim3 grid(rz_div_up(W_out, RZ_THREADS), (uint32_t)H_out, (uint32_t)n);
-    if (is_f32)
-        hipLaunchKernelGGL(resize_nearest_f32_kernel, grid, dim3(RZ_THREADS), 0, stream, (const float*)src, src_image_stride, src_row_stride, H, W,
-                           H_out, W_out, yidx, xidx, (float*)out, out_image_stride, out_row_stride);
-    else
-        hipLaunchKernelGGL(resize_nearest_u8_kernel, grid, dim3(RZ_THREADS), 0, stream, (const uint8_t*)src, src_image_stride, src_row_stride, H, W, C,
-                           H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride, epilogue);
-    return hipGetLastError();
+    if (int rc = resize_check("resize_nearest_u8", src, out, src_image_stride, src_row_stride, n, H, W, C, H_out, W_out, out_image_stride,
+                              out_row_stride, epilogue))
+        return rc;
+    if ((!yidx && H_out != H) || (!xidx && W_out != W))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "resize_nearest_u8: a NULL index table is the identity and needs equal sizes");
+    GSR_HIP(resize_launch_nearest(src, src_image_stride, src_row_stride, n, H, W, C, 0, H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride,
+                                  epilogue, (hipStream_t)stream), "resize_nearest_u8");
+    return GSR_OK;
+}
+
+extern "C" int gsr_resize_nearest_f32(const float* src, long long src_image_stride, long long src_row_stride, int n, int H, int W, int H_out, int W_out,
+                                      const int32_t* yidx, const int32_t* xidx, float* out, long long out_image_stride, long long out_row_stride,
+                                      void* stream)
+{
+    if (int rc = resize_check("resize_nearest_f32", src, out, src_image_stride, src_row_stride, n, H, W, 1, H_out, W_out, out_image_stride,
+                              out_row_stride, GSR_RESIZE_U8))
+        return rc;
+    if ((!yidx && H_out != H) || (!xidx && W_out != W))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "resize_nearest_f32: a NULL index table is the identity and needs equal sizes");
+    GSR_HIP(resize_launch_nearest(src, src_image_stride, src_row_stride, n, H, W, 1, 1, H_out, W_out, yidx, xidx, out, out_image_stride, out_row_stride,
+                                  GSR_RESIZE_U8, (hipStream_t)stream), "resize_nearest_f32");
+    return GSR_OK;
 }

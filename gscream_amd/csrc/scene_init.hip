@@ -22,7 +22,8 @@
 #include <limits.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
+#include "gsr_carve.h"
 #include "gsr_reduce.h"
 #include "gsr_scan.h"
 
@@ -218,9 +219,9 @@ static GsiSortWork gsi_sort_carve(void* base, int N)
     return w;
 }
 
-size_t gsi_sort_workspace_bytes(int N) { return gsi_sort_carve(nullptr, N).bytes; }
+static size_t gsi_sort_workspace_bytes(int N) { return gsi_sort_carve(nullptr, N).bytes; }
 
-hipError_t gsi_sort_launch(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, hipStream_t stream)
+static hipError_t gsi_sort_launch(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, hipStream_t stream)
 {
     if (N == 0) return hipSuccess;
     hipError_t e;
@@ -429,8 +430,6 @@ static GsiVoxWork gsi_vox_carve(void* base, int N)
     return w;
 }
 
-size_t gsi_voxelize_workspace_bytes(int N) { return gsi_vox_carve(nullptr, N).bytes; }
-
 template <typename T>
 static hipError_t gsi_voxelize_typed(int N, const T* pts, double v_host, const float* v_dev, void* workspace, T* out, int32_t* info,
                                      hipStream_t stream)
@@ -446,14 +445,6 @@ static hipError_t gsi_voxelize_typed(int N, const T* pts, double v_host, const f
     hipLaunchKernelGGL(gsi_vox_top_kernel, dim3(1), dim3(1024), 0, stream, nb, w.bsum, w.head, v_host, v_dev, info);
     hipLaunchKernelGGL(gsi_vox_place_kernel<T>, dim3(nb), dim3(GSI_THREADS), 0, stream, N, w.keys, w.bsum, w.head, v_host, v_dev, out);
     return hipGetLastError();
-}
-
-hipError_t gsi_voxelize_launch(int N, int fp64, const void* points, double v_host, const float* v_dev, void* workspace, void* out,
-                               int32_t* info, hipStream_t stream)
-{
-    if (N == 0) return hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream);
-    return fp64 ? gsi_voxelize_typed<double>(N, (const double*)points, v_host, v_dev, workspace, (double*)out, info, stream)
-                : gsi_voxelize_typed<float>(N, (const float*)points, v_host, v_dev, workspace, (float*)out, info, stream);
 }
 
 // ---- k-th smallest ------------------------------------------------------------------------------------------------------------
@@ -518,25 +509,6 @@ static GsiKthWork gsi_kth_carve(void* base)
     return { ws, c.total() };
 }
 
-size_t gsi_kth_workspace_bytes(int N)
-{
-    (void)N;
-    return gsi_kth_carve(nullptr).bytes;
-}
-
-hipError_t gsi_kth_launch(int N, int k, const float* values, void* workspace, float* out, hipStream_t stream)
-{
-    uint32_t* ws = gsi_kth_carve(workspace).ws;
-    hipError_t e;
-    if ((e = hipMemsetAsync(ws, 0, (size_t)GSI_KTH_WORDS * 4, stream)) != hipSuccess) return e;
-    const int nb = gsi_blocks(N, GSI_KTH_TILE);
-    for (int level = 0; level < 4; level++) {
-        hipLaunchKernelGGL(gsi_kth_hist_kernel, dim3(nb), dim3(GSI_THREADS), 0, stream, N, level, values, ws);
-        hipLaunchKernelGGL(gsi_kth_pick_kernel, dim3(1), dim3(256), 0, stream, level, k, ws, out);
-    }
-    return hipGetLastError();
-}
-
 // ---- the state create_from_pcd leaves -----------------------------------------------------------------------------------------
 // max of fp32 values through integer atomics (the word starts at -inf): the result does not depend on the order of arrival
 __device__ __forceinline__ void gsi_atomic_max_f32(float* addr, float v)
@@ -572,15 +544,72 @@ __global__ void __launch_bounds__(GSI_THREADS) gsi_fill_kernel(int M, int K, int
     }
 }
 
-hipError_t gsi_fill_launch(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
-                           float* feat, float* rotation, float* opac, float* unc, float* radii, float* xyz_max, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+#define GSI_MAX_N (1 << 30)  // (no accepted N wraps a carve: the largest piece is N keys of 8 bytes = 2^33)
+extern "C" int gsr_sort_block_keys(void) { return GSR_SORT_BLOCK_KEYS; }
+
+extern "C" size_t gsr_sort_keys_workspace_bytes(int N) { return N < 0 || N > GSI_MAX_N ? 0 : gsi_sort_workspace_bytes(N); }
+
+extern "C" int gsr_sort_keys_u64(int N, const uint64_t* keys_in, uint64_t* keys_out, void* workspace, void* stream)
 {
-    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)xyz_max, (int)0xff800000u, 3, stream);  // -inf
-    if (e != hipSuccess || M == 0) return e;
-    size_t widest = (size_t)M * 6;
-    if ((size_t)M * K * 3 > widest) widest = (size_t)M * K * 3;
-    if ((size_t)M * F > widest) widest = (size_t)M * F;
+    if (N < 0 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "sort keys: N=%d (need 0 <= N <= 2^30)", N);
+    if (N == 0) return GSR_OK;
+    if (!keys_in || !keys_out || !workspace) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "sort keys: keys_in, keys_out or workspace is NULL");
+    GSR_HIP(gsi_sort_launch(N, keys_in, keys_out, workspace, (hipStream_t)stream), "sort keys");
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_voxelize_workspace_bytes(int N) { return N < 0 || N > GSI_MAX_N ? 0 : gsi_vox_carve(nullptr, N).bytes; }
+
+extern "C" int gsr_voxelize(int N, int fp64, const void* points, double voxel_size, const float* voxel_size_dev, void* workspace, void* out,
+                            int32_t* info, void* stream_)
+{
+    if (N < 0 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: N=%d (need 0 <= N <= 2^30)", N);
+    if (fp64 != 0 && fp64 != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: fp64=%d (need 0 or 1)", fp64);
+    if (!info || (N > 0 && (!points || !workspace || !out)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "voxelize: points, workspace, out or info is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N == 0) GSR_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream), "voxelize");
+    else if (fp64) GSR_HIP(gsi_voxelize_typed<double>(N, (const double*)points, voxel_size, voxel_size_dev, workspace, (double*)out, info, stream), "voxelize");
+    else GSR_HIP(gsi_voxelize_typed<float>(N, (const float*)points, voxel_size, voxel_size_dev, workspace, (float*)out, info, stream), "voxelize");
+    return GSR_OK;
+}
+
+extern "C" size_t gsr_kth_smallest_workspace_bytes(int N) { return N < 1 || N > GSI_MAX_N ? 0 : gsi_kth_carve(nullptr).bytes; }
+
+extern "C" int gsr_kth_smallest_f32(int N, int k, const float* values, void* workspace, float* out, void* stream_)
+{
+    if (N < 1 || N > GSI_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: N=%d (need 1 <= N <= 2^30)", N);
+    if (k < 1 || k > N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: k=%d out of range for %d values (need 1 <= k <= N)", k, N);
+    if (!values || !workspace || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "kth smallest: values, workspace or out is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    uint32_t* ws = gsi_kth_carve(workspace).ws;
+    GSR_HIP(hipMemsetAsync(ws, 0, (size_t)GSI_KTH_WORDS * 4, stream), "kth smallest");
+    const int nb = gsi_blocks(N, GSI_KTH_TILE);
+    for (int level = 0; level < 4; level++) {
+        hipLaunchKernelGGL(gsi_kth_hist_kernel, dim3(nb), dim3(GSI_THREADS), 0, stream, N, level, values, ws);
+        hipLaunchKernelGGL(gsi_kth_pick_kernel, dim3(1), dim3(256), 0, stream, level, k, ws, out);
+    }
+    GSR_HIP(hipGetLastError(), "kth smallest");
+    return GSR_OK;
+}
+
+extern "C" int gsr_scene_init_fill(int M, int K, int F, const float* anchors, const float* dist2, float opacity, float* scaling, float* offset,
+                                   float* anchor_feat, float* rotation, float* opacity_out, float* uncertainty_out, float* max_radii2D,
+                                   float* xyz_max, void* stream_)
+{
+    if (M < 0 || K < 0 || F < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: M=%d K=%d F=%d (need all >= 0)", M, K, F);
+    const int64_t widest = (int64_t)M * (3 * (int64_t)K > (int64_t)F ? (3 * (int64_t)K > 6 ? 3 * (int64_t)K : 6) : ((int64_t)F > 6 ? (int64_t)F : 6));
+    if (widest >= 0x7fffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: M=%d K=%d F=%d (need M * max(3 K, F, 6) < 2^31)", M, K, F);
+    if (!xyz_max) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: xyz_max is NULL");
+    if (M > 0 && (!anchors || !dist2 || !scaling || !rotation || !opacity_out || !uncertainty_out || !max_radii2D || (K > 0 && !offset)
+                  || (F > 0 && !anchor_feat)))
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "scene init fill: a required pointer is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    GSR_HIP(hipMemsetD32Async((hipDeviceptr_t)xyz_max, (int)0xff800000u, 3, stream), "scene init fill");  // -inf
+    if (M == 0) return GSR_OK;
     hipLaunchKernelGGL(gsi_fill_kernel, dim3((unsigned)((widest + GSI_THREADS - 1) / GSI_THREADS)), dim3(GSI_THREADS), 0, stream, M, K, F, anchors,
-                       dist2, opacity, scaling, offset, feat, rotation, opac, unc, radii, xyz_max);
-    return hipGetLastError();
+                       dist2, opacity, scaling, offset, anchor_feat, rotation, opacity_out, uncertainty_out, max_radii2D, xyz_max);
+    GSR_HIP(hipGetLastError(), "scene init fill");
+    return GSR_OK;
 }

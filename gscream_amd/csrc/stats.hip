@@ -11,7 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gsr_common.h"
+#include "gsr_api.h"
 
 // One thread per (visible anchor, offset): neighbouring lanes touch neighbouring words of every [N*K] array (the first version
 // had one thread per anchor walk its K offsets: every access strided by 4 K bytes, 39 us for ~50 MB; this one is bandwidth-
@@ -59,14 +59,21 @@ __global__ void __launch_bounds__(256) gst_training_stats_kernel(
     }
 }
 
-hipError_t gst_launch_training_stats(int Nv, int K, int M, const int32_t* visible, const float* neural_opacity,
-                                     const uint8_t* selection, const uint32_t* first, const uint8_t* update_filter,
-                                     const float* viewspace_grad, float* opacity_accum, float* anchor_demon,
-                                     float* offset_gradient_accum, float* offset_denom, hipStream_t stream)
+// ---- C entry points (include/gsraster.h): check the arguments, launch ----
+extern "C" int gsr_training_stats(int Nv, int K, int M, const int32_t* visible, const float* neural_opacity, const uint8_t* selection,
+                                  const uint32_t* first, const uint8_t* update_filter, const float* viewspace_grad,
+                                  float* opacity_accum, float* anchor_demon, float* offset_gradient_accum,
+                                  float* offset_denom, void* stream)
 {
-    if (Nv <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gst_training_stats_kernel, dim3((unsigned)(((size_t)Nv * K + 255) / 256)), dim3(256), 0, stream, Nv, K, M, visible, neural_opacity,
-                       selection, first, update_filter, viewspace_grad, opacity_accum, anchor_demon, offset_gradient_accum,
+    if (Nv < 0 || K < 1 || M < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "training stats: bad sizes Nv=%d K=%d M=%d", Nv, K, M);
+    if (Nv == 0) return GSR_OK;
+    if (!neural_opacity || !selection || !first || !opacity_accum || !anchor_demon || !offset_gradient_accum || !offset_denom)
+        return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "training stats: a required pointer is NULL");
+    // update_filter / viewspace_grad may be NULL only if no offset was selected (M = 0); the kernel then never reads them
+    if (M > 0 && (!update_filter || !viewspace_grad)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "training stats: update_filter / viewspace_grad is NULL with M = %d", M);
+    hipLaunchKernelGGL(gst_training_stats_kernel, dim3((unsigned)(((size_t)Nv * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Nv, K, M, visible,
+                       neural_opacity, selection, first, update_filter, viewspace_grad, opacity_accum, anchor_demon, offset_gradient_accum,
                        offset_denom);
-    return hipGetLastError();
+    GSR_HIP(hipGetLastError(), "training stats");
+    return GSR_OK;
 }
