@@ -27,7 +27,8 @@ _CONSTANTS = ("NEED_CAPACITY", "ADJUST_MAX_COPIES", "ADJUST_COPY", "ADJUST_CLAMP
               "ADJUST_ANCHOR_STAT", "ADAM_MAX_TENSORS", "FRAME_MAX_PANELS", "FRAME_QUANT", "FRAME_QUANT_CLAMP", "FRAME_ABSDIFF", "FRAME_NORMAL",
               "FRAME_CMAP_CV", "FRAME_CMAP_MPL_ALIGNED", "FRAME_CMAP_MPL", "PNG_CHUNK", "PNG_HEADER_BYTES", "PNG_FILTER_ADAPTIVE",
               "PNG_PIECE_IDAT", "PNG_PIECE_START", "JPEG_HEADER_BYTES", "JPEG_INTERVAL_BLOCKS", "JPEG_NEED_CAPACITY", "RESIZE_HORIZONTAL",
-              "RESIZE_VERTICAL", "RESIZE_U8", "RESIZE_DIV255", "RESIZE_GT0")
+              "RESIZE_VERTICAL", "RESIZE_U8", "RESIZE_DIV255", "RESIZE_GT0", "METRICS_CLAMP", "METRICS_QUANTIZE", "LPIPS_NORMALIZE",
+              "LPIPS_SCALING", "SORT_BLOCK_KEYS", "VOXELIZE_NONFINITE", "VOXELIZE_CELL_RANGE", "VOXELIZE_KEY_WIDTH")
 globals().update({name: _ABI.constants["GSR_" + name] for name in _CONSTANTS})
 # what the header holds as comments only; the lengths are held to its constants
 STAGE_NAMES = ("preprocess", "count_scan", "scatter", "tile_sort", "blend_forward", "blend_backward", "gauss_backward")
@@ -68,13 +69,18 @@ class FramePanel(ctypes.Structure):
                 ("width", ctypes.c_int32), ("mode", ctypes.c_int32)]
 
 
+class LayoutPiece(ctypes.Structure):
+    """gsr_layout_piece: one array of a rasterizer workspace as gsr_workspace_layout reports it (name: a C string the library owns)."""
+    _fields_ = [("name", ctypes.c_void_p), ("offset", ctypes.c_size_t), ("count", ctypes.c_size_t), ("elem_size", ctypes.c_size_t)]
+
+
 class Profile(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double * NUM_STAGES), ("launches", ctypes.c_int64 * NUM_STAGES)]
 
 
 #: the header's structs that have a class here (tests hold every field to the header); a pointer to one is typed, any other is void*
 STRUCTS = {"gsr_stage1_result": Stage1Result, "gsr_tuning": Tuning, "gsr_adjust_copy": AdjustCopy, "gsr_adam_tensor": AdamTensor,
-           "gsr_frame_panel": FramePanel, "gsr_profile": Profile}
+           "gsr_frame_panel": FramePanel, "gsr_profile": Profile, "gsr_layout_piece": LayoutPiece}
 _lib = None
 
 

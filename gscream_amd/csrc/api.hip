@@ -123,6 +123,34 @@ extern "C" size_t gsr_image_bytes(int P, int W, int H) { return gsr_carve_image(
 extern "C" size_t gsr_binning_bytes(int R) { return gsr_carve_binning(nullptr, R).bytes; }
 extern "C" size_t gsr_backward_scratch_bytes(int P, int num_slots) { return gsr_carve_backward_scratch(nullptr, P, num_slots).bytes; }
 
+extern "C" int gsr_workspace_layout(int which, int P, int W, int H, int R, gsr_layout_piece* out_host, int capacity)
+{
+    if (capacity < 0 || (capacity > 0 && !out_host)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "out_host is NULL or the capacity negative (%d)", capacity);
+    GsrCarveRecord record = { out_host, capacity, 0 };
+    switch (which) {
+    case GSR_LAYOUT_GEOM: gsr_carve_geom(nullptr, P, &record); break;
+    case GSR_LAYOUT_IMAGE: gsr_carve_image(nullptr, P, W, H, &record); break;
+    case GSR_LAYOUT_BINNING: gsr_carve_binning(nullptr, R, &record); break;
+    case GSR_LAYOUT_BACKWARD_SCRATCH: gsr_carve_backward_scratch(nullptr, P, R, &record); break;
+    default: return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "unknown workspace %d (GSR_LAYOUT_*)", which);
+    }
+    return record.count;
+}
+extern "C" int gsr_layout_constant(int which)
+{
+    switch (which) {
+    case GSR_CONSTANT_SEG1: return GSR_SEG1;
+    case GSR_CONSTANT_SEG2: return GSR_SEG2;
+    case GSR_CONSTANT_SEG_MAX: return GSR_SEG_MAX;
+    case GSR_CONSTANT_XCD_CHUNK: return GSR_XCD_CHUNK;
+    }
+    return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "unknown constant %d (GSR_CONSTANT_*)", which);
+}
+extern "C" int gsr_layout_ckpt_pos(int k, int L) { return gsr_ckpt_pos(k, L); }
+extern "C" int gsr_layout_num_chunks(int P) { return gsr_num_chunks(P); }
+extern "C" int gsr_layout_xcd_tiles(int T) { return gsr_xcd_tiles(T); }
+extern "C" int gsr_layout_xcd_tile(int xcd, int i, int T) { return gsr_xcd_tile(xcd, i, T); }
+
 static bool gsr_partial_sort(const gsr_tuning* tuning) { return !(tuning && tuning->disable_partial_sort); }
 static bool gsr_inference(const gsr_tuning* tuning) { return tuning && tuning->inference; }
 static int gsr_forced_bands(const gsr_tuning* tuning) { return tuning ? tuning->scatter_bands : 0; }

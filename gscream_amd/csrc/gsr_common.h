@@ -41,7 +41,6 @@
 #include "gsr_carve.h"
 
 #define GSR_TILE 16
-// (plain #defines where gscream_amd/_layout.py mirrors the value: a -D of one of them collides instead of building a library the mirror mis-decodes)
 #define GSR_MAX_CHUNKS 256       // NB: rows of the (chunk, tile) count table = workgroups of the histogram / scatter launches: one per CU
                                  // (measured at 1M Gaussians: 2048 x 128 threads 47 + 47 us, 1024 x 256: 36 + 44, 512 x 512: 32 + 41, 256 x 1024: 29 + 38)
 #define GSR_CHUNK_GAUSS 1024     // Gaussians per chunk at least (small clouds get fewer chunks, large ones GSR_MAX_CHUNKS bigger chunks)
@@ -246,39 +245,39 @@ static inline int gsr_num_chunks(int P)
 struct GsrGrid { int gx, gy; };
 static inline GsrGrid gsr_tile_grid(int W, int H) { return { (W + GSR_TILE - 1) / GSR_TILE, (H + GSR_TILE - 1) / GSR_TILE }; }
 
-static inline GsrGeom gsr_carve_geom(void* base, int P)
+static inline GsrGeom gsr_carve_geom(void* base, int P, GsrCarveRecord* record = nullptr)
 {
     GsrGeom g;
-    GsrCarver c(base);
+    GsrCarver c(base, record);
     size_t p = (size_t)(P > 0 ? P : 1);
-    g.rec = c.take<GsrRec>(p);
-    g.rect = c.take<uint2>(p);
-    g.depthkey = c.take<uint32_t>(p);
-    g.tiles = c.take<uint32_t>(p);
-    g.offsets = c.take<uint32_t>(p);
-    g.tmask = c.take<unsigned long long>(p);
-    g.clamped = c.take<uint8_t>(p * 3);
-    g.scan_sums = c.take<uint32_t>(GSR_MAX_CHUNKS + 1);  // per-chunk instance totals (gsr_num_chunks(P) <= GSR_MAX_CHUNKS)
+    g.rec = c.take<GsrRec>("rec", p);
+    g.rect = c.take<uint2>("rect", p);
+    g.depthkey = c.take<uint32_t>("depthkey", p);
+    g.tiles = c.take<uint32_t>("tiles", p);
+    g.offsets = c.take<uint32_t>("offsets", p);
+    g.tmask = c.take<unsigned long long>("tmask", p);
+    g.clamped = c.take<uint8_t>("clamped", p * 3);
+    g.scan_sums = c.take<uint32_t>("scan_sums", GSR_MAX_CHUNKS + 1);  // per-chunk instance totals (gsr_num_chunks(P) <= GSR_MAX_CHUNKS)
     g.bytes = c.total();
     return g;
 }
 
-static inline GsrImage gsr_carve_image(void* base, int P, int W, int H)
+static inline GsrImage gsr_carve_image(void* base, int P, int W, int H, GsrCarveRecord* record = nullptr)
 {
     GsrImage im;
-    GsrCarver c(base);
+    GsrCarver c(base, record);
     const GsrGrid grid = gsr_tile_grid(W, H);
     size_t gx = grid.gx, gy = grid.gy;
     size_t T = gx * gy > 0 ? gx * gy : 1, N = (size_t)W * H > 0 ? (size_t)W * H : 1;
-    im.ranges = c.take<uint2>(T);
-    im.final_T = c.take<float>(N);
-    im.n_contrib = c.take<uint32_t>(N);
+    im.ranges = c.take<uint2>("ranges", T);
+    im.final_T = c.take<float>("final_T", N);
+    im.n_contrib = c.take<uint32_t>("n_contrib", N);
     // [chunks][T] count table; beyond the LDS tile limit (global-counter fallback) only T cursor words are needed
-    im.table = c.take<uint32_t>((T > GSR_MAX_TILES_LDS ? (size_t)1 : (size_t)gsr_num_chunks(P)) * T);
-    im.tile_count = c.take<uint32_t>(T);
-    im.tile_work = c.take<uint32_t>(T);
-    im.sorted_len = c.take<uint32_t>(T);
-    im.need_full = c.take<uint32_t>(T);
+    im.table = c.take<uint32_t>("table", (T > GSR_MAX_TILES_LDS ? (size_t)1 : (size_t)gsr_num_chunks(P)) * T);
+    im.tile_count = c.take<uint32_t>("tile_count", T);
+    im.tile_work = c.take<uint32_t>("tile_work", T);
+    im.sorted_len = c.take<uint32_t>("sorted_len", T);
+    im.need_full = c.take<uint32_t>("need_full", T);
     im.N = N;
     {
         // The occlusion cut-off's mass tables (GSR_OCC_COPIES * T * GSR_OCC_BUCKETS words = 5 KB per tile) live only from the preprocess
@@ -288,28 +287,28 @@ static inline GsrImage gsr_carve_image(void* base, int P, int W, int H)
         // keeps alive (round 5).
         const size_t ck = (size_t)GSR_CKPT_PLANES * ((N + 3) & ~(size_t)3) * 4;
         const size_t oc = T <= GSR_OCC_MAX_TILES ? (size_t)GSR_OCC_COPIES * T * GSR_OCC_BUCKETS * 4 : 4;
-        im.ckpt = c.alias<float>();
-        im.occ_mass = c.alias<uint32_t>();
+        im.ckpt = c.alias<float>("ckpt", ck / 4);
+        im.occ_mass = c.alias<uint32_t>("occ_mass", oc / 4);
         c.skip(ck > oc ? ck : oc);
     }
-    im.info = c.take<uint32_t>(4);
-    im.qresume = c.take<uint32_t>(4 * T);
-    im.qorder = c.take<uint32_t>((size_t)32 * gsr_xcd_tiles((int)T));
-    im.occ_cut = c.take<uint32_t>(T);
-    im.occ_drop = c.take<uint32_t>(GSR_MAX_CHUNKS);
-    im.tile_group = c.take<uint32_t>(T / 64 + 1);
+    im.info = c.take<uint32_t>("info", 4);
+    im.qresume = c.take<uint32_t>("qresume", 4 * T);
+    im.qorder = c.take<uint32_t>("qorder", (size_t)32 * gsr_xcd_tiles((int)T));
+    im.occ_cut = c.take<uint32_t>("occ_cut", T);
+    im.occ_drop = c.take<uint32_t>("occ_drop", GSR_MAX_CHUNKS);
+    im.tile_group = c.take<uint32_t>("tile_group", T / 64 + 1);
     im.bytes = c.total();
     return im;
 }
 
-static inline GsrBinning gsr_carve_binning(void* base, int R)
+static inline GsrBinning gsr_carve_binning(void* base, int R, GsrCarveRecord* record = nullptr)
 {
     GsrBinning bn;
-    GsrCarver c(base);
+    GsrCarver c(base, record);
     size_t r = (size_t)(R > 0 ? R : 1);
-    bn.seg_keys = c.take<unsigned long long>(r);
-    bn.point_list = c.take<uint32_t>(r);
-    bn.slot_written = c.take<uint8_t>(r);
+    bn.seg_keys = c.take<unsigned long long>("seg_keys", r);
+    bn.point_list = c.take<uint32_t>("point_list", r);
+    bn.slot_written = c.take<uint8_t>("slot_written", r);
     bn.bytes = c.total();
     return bn;
 }
@@ -321,12 +320,12 @@ struct GsrBackwardScratch {
     uint32_t* heavy;
     size_t bytes;
 };
-static inline GsrBackwardScratch gsr_carve_backward_scratch(void* base, int P, int num_slots)
+static inline GsrBackwardScratch gsr_carve_backward_scratch(void* base, int P, int num_slots, GsrCarveRecord* record = nullptr)
 {
     GsrBackwardScratch s;
-    GsrCarver c(base);
-    s.slots = c.take<float>((size_t)(num_slots > 0 ? num_slots : 1) * GSR_SLOT_FLOATS);
-    s.heavy = c.take<uint32_t>((size_t)(P > 0 ? P : 1) / 64 + 18);
+    GsrCarver c(base, record);
+    s.slots = c.take<float>("slots", (size_t)(num_slots > 0 ? num_slots : 1) * GSR_SLOT_FLOATS);
+    s.heavy = c.take<uint32_t>("heavy", (size_t)(P > 0 ? P : 1) / 64 + 18);
     s.bytes = c.total();
     return s;
 }

@@ -31,7 +31,7 @@ __all__ = ["LPIPS", "lpips_views", "pack_conv3x3", "conv3x3_relu"]
 force_torch = False
 last_path = None  # "hip" / "torch": the path the last call took
 
-NORMALIZE, SCALING = 1, 2  # GSR_LPIPS_NORMALIZE, GSR_LPIPS_SCALING
+NORMALIZE, SCALING = _native.LPIPS_NORMALIZE, _native.LPIPS_SCALING
 CONV_KC, CONV_NB = 8, 64   # LPIPS_CONV_KC, LPIPS_CONV_NB: the packed layout of include/gsraster.h
 WIDTHS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
           (512, 512), (512, 512), (512, 512))

@@ -40,7 +40,7 @@ last_path = None  # "hip" / "torch": the path the last call took
 
 MAX_PLANES = 65535         # gsr_image_metrics: B*C per call
 MAX_ELEMENTS = 0x7FFFFF00  # its limit on C*H*W
-CLAMP, QUANTIZE = 1, 2     # GSR_METRICS_CLAMP, GSR_METRICS_QUANTIZE
+CLAMP, QUANTIZE = _native.METRICS_CLAMP, _native.METRICS_QUANTIZE
 C1, C2, SSIM_EPS = 1e-4, 9e-4, 1e-12
 FIELDS = ("l1", "mse", "psnr", "ssim", "l1_masked", "mse_masked", "psnr_masked", "ssim_masked")
 

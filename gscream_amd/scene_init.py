@@ -24,8 +24,8 @@ from .simple_knn import distCUDA2
 
 __all__ = ["SORT_BLOCK_KEYS", "sort_keys", "voxelize_sample", "kth_smallest", "create_from_pcd", "model_from_points", "opacity_init"]
 
-SORT_BLOCK_KEYS = 2048  # include/gsraster.h GSR_SORT_BLOCK_KEYS: keys one workgroup of the sort ranks (tests size their cases by it)
-NONFINITE, CELL_RANGE, KEY_WIDTH = 1, 2, 4  # GSR_VOXELIZE_* flag bits of info[1]
+SORT_BLOCK_KEYS = _native.SORT_BLOCK_KEYS  # keys one workgroup of the sort ranks (tests size their cases by it)
+NONFINITE, CELL_RANGE, KEY_WIDTH = _native.VOXELIZE_NONFINITE, _native.VOXELIZE_CELL_RANGE, _native.VOXELIZE_KEY_WIDTH  # flag bits of info[1]
 last_path = None  # "hip" / "torch": the path the last voxelize_sample() / kth_smallest() took
 
 _FLAG_TEXT = (

@@ -108,7 +108,7 @@ typedef struct gsr_profile {
 const char* gsr_version(void);
 /* Integer version of this header's binary interface: bumped whenever an entry point's argument list, a struct layout or a
  * workspace size formula changes incompatibly.  Bindings compare it with GSR_ABI_VERSION at load time. */
-#define GSR_ABI_VERSION 8
+#define GSR_ABI_VERSION 9
 int gsr_abi_version(void);
 const char* gsr_last_error(void);
 /* Forget what the calling thread's previous calls taught the launch heuristics that learn from feedback (ABI 7): today the partial
@@ -128,6 +128,30 @@ size_t gsr_image_bytes(int P, int W, int H);  /* per-pixel / per-tile state kept
                                                  touched only when gsr_tuning.occlusion_cut is set) */
 size_t gsr_binning_bytes(int R);              /* per-instance state: sorted point list (+ sort keys)  */
 size_t gsr_backward_scratch_bytes(int P, int num_slots); /* per-instance gradient slots + the heavy-group list of the per-Gaussian backward */
+
+/* ---- what is where in those four workspaces (ABI 9): for tests and debugging tools that decode a forward's state (gscream_amd/_layout.py).
+ * The library answers from the very walk that carves the caller's pointer, run without one, and from its own compiled constants:
+ * a build with other internal values is decoded by what it says.  Host-only: no stream, no device needed.
+ * gsr_workspace_layout writes the first `capacity` pieces of workspace `which` (sized like its gsr_*_bytes query: geometry P; image P, W, H;
+ * binning R; backward scratch P and R = num_slots; the other arguments are ignored) to out_host, in carving order, and returns how many
+ * pieces there are, whatever the capacity (out_host may be NULL with capacity 0), or a negative gsr_status.  Pieces do not overlap,
+ * except that the image's `ckpt` and `occ_mass` share one area (the masses are dead before the checkpoints are written). */
+enum { GSR_LAYOUT_GEOM = 0, GSR_LAYOUT_IMAGE, GSR_LAYOUT_BINNING, GSR_LAYOUT_BACKWARD_SCRATCH };
+typedef struct gsr_layout_piece {
+    const char* name; /* the array's name inside the library (a string the library owns) */
+    size_t offset;    /* bytes from the workspace's start */
+    size_t count;     /* elements */
+    size_t elem_size; /* bytes per element */
+} gsr_layout_piece;
+int gsr_workspace_layout(int which, int P, int W, int H, int R, gsr_layout_piece* out_host, int capacity);
+/* Depth segments per tile in the first tier / behind it / in all (= checkpoint slots of `ckpt`), and consecutive tiles an XCD is dealt at
+ * a time; gsr_layout_constant returns the value, or a negative gsr_status for an unknown `which`. */
+enum { GSR_CONSTANT_SEG1 = 0, GSR_CONSTANT_SEG2, GSR_CONSTANT_SEG_MAX, GSR_CONSTANT_XCD_CHUNK };
+int gsr_layout_constant(int which);
+int gsr_layout_ckpt_pos(int k, int L);            /* list position of checkpoint k = 0 .. SEG_MAX - 2 at segment length L (64 up to 4096 tiles, 128 beyond) */
+int gsr_layout_num_chunks(int P);                 /* rows of the image's (chunk, tile) count table for P Gaussians (one row when the tiles outgrow the LDS histogram) */
+int gsr_layout_xcd_tiles(int T);                  /* tile slots per XCD */
+int gsr_layout_xcd_tile(int xcd, int i, int T);   /* the i-th tile of XCD `xcd`, -1 = none */
 
 /*
  * Forward, stage 1 of 2: per-Gaussian preprocess + tile histogram + scans.

@@ -47,6 +47,7 @@ HOST_PARAMS = {
     ("gsr_forward", "tuning"): "gsr_tuning struct on the host",
     ("gsr_backward", "tuning"): "gsr_tuning struct on the host",
     ("gsr_profile_end", "out_host"): "gsr_profile struct on the host",
+    ("gsr_workspace_layout", "out_host"): "array of gsr_layout_piece on the host: the query runs no kernel and touches no device memory",
     ("gsr_decode_count", "weights"): "host array of 16 device pointers (each checked as const)",
     ("gsr_decode_emit", "weights"): "host array of 16 device pointers (each checked as const)",
     ("gsr_decode_backward", "weights"): "host array of 16 device pointers (each checked as const)",

@@ -1,6 +1,8 @@
 // carve_check.cpp -- GsrCarver on its own, as a host program (tests/test_workspace_sizes.py builds it with
 // -fsanitize=address,undefined and runs it): every piece on its alignment, pieces in order and apart, the null-base walk with the
-// same total and no pointer, an alias + skip pair as large as its larger user, a wrapping count caught.
+// same total and no pointer, an alias + skip pair as large as its larger user, a wrapping count caught; and the record of named
+// pieces: every offset = pointer - base, the null-base walk records the same table, an alias + skip pair lists both users at one
+// offset, unnamed pieces are left out, a short record array is counted past and not overrun.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -103,6 +105,51 @@ int main()
         GsrCarver e(nullptr);
         e.skip((size_t)-1 - 100);              // the rounding itself wraps
         CHECK(!e.ok());
+    }
+    // the record: a walk on a workspace and the same walk on a null base note the same table, each offset = pointer - base
+    {
+        auto walk = [](GsrCarver& c, char** at) {
+            at[0] = (char*)c.take<Bytes<64>>("rec", 3);
+            (void)c.take<uint32_t>(5);  // unnamed: cut, not recorded
+            at[1] = (char*)c.take<Bytes<8>>("rect", 65);
+            at[2] = (char*)c.alias<float>("ckpt", 648);
+            at[3] = (char*)c.alias<uint32_t>("occ_mass", 1280);
+            c.skip(5120);
+            at[4] = (char*)c.take<uint8_t>("flags", 0);
+            at[5] = (char*)c.take<Bytes<12>>("tail", 7, 16);
+        };
+        const char* names[] = {"rec", "rect", "ckpt", "occ_mass", "flags", "tail"};
+        const size_t counts[] = {3, 65, 648, 1280, 0, 7}, sizes[] = {64, 8, 4, 4, 1, 12};
+        alignas(256) static char area[8192];
+        gsr_layout_piece with_base[6], without[6];
+        GsrCarveRecord ra = {with_base, 6, 0}, rq = {without, 6, 0};
+        GsrCarver c(area, &ra), q(nullptr, &rq);
+        char *at[6], *none[6];
+        walk(c, at);
+        walk(q, none);
+        CHECK(ra.count == 6 && rq.count == 6 && c.bytes() == q.bytes() && c.bytes() <= sizeof area);
+        for (int i = 0; i < 6; i++) {
+            CHECK(none[i] == nullptr && with_base[i].offset == (size_t)(at[i] - area) && without[i].offset == with_base[i].offset);
+            CHECK(!strcmp(with_base[i].name, names[i]) && !strcmp(without[i].name, names[i]));
+            CHECK(with_base[i].count == counts[i] && without[i].count == counts[i]);
+            CHECK(with_base[i].elem_size == sizes[i] && without[i].elem_size == sizes[i]);
+        }
+        CHECK(with_base[2].offset == with_base[3].offset && with_base[4].offset == with_base[2].offset + 5120);
+        // the same walk without a record leaves the same pointers
+        GsrCarver plain(area);
+        char* again[6];
+        walk(plain, again);
+        for (int i = 0; i < 6; i++) CHECK(again[i] == at[i]);
+        CHECK(plain.bytes() == c.bytes());
+        // a record array of two (heap: AddressSanitizer watches its end), then of none: filled as far as it goes, all six counted
+        gsr_layout_piece* two = (gsr_layout_piece*)malloc(2 * sizeof(gsr_layout_piece));
+        CHECK(two);
+        GsrCarveRecord rs = {two, 2, 0}, r0 = {nullptr, 0, 0};
+        GsrCarver s(nullptr, &rs), z(nullptr, &r0);
+        walk(s, none);
+        walk(z, none);
+        CHECK(rs.count == 6 && r0.count == 6 && !strcmp(two[1].name, "rect") && two[1].offset == with_base[1].offset);
+        free(two);
     }
     printf("carve_check OK\n");
     return 0;

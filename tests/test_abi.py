@@ -98,8 +98,8 @@ def test_header_is_read_once_and_a_missing_one_is_fatal(monkeypatch, tmp_path):
 
 
 def test_the_real_header_as_a_whole(native_lib):
-    assert len(ABI.functions) == 80 and _native.EXPORTED_SYMBOLS == tuple(ABI.functions)
-    assert ABI.constants["GSR_ABI_VERSION"] == _native.ABI_VERSION == native_lib.gsr_abi_version() == 8
+    assert len(ABI.functions) == 86 and _native.EXPORTED_SYMBOLS == tuple(ABI.functions)
+    assert ABI.constants["GSR_ABI_VERSION"] == _native.ABI_VERSION == native_lib.gsr_abi_version() == 9
     assert native_lib.gsr_version().startswith(b"gsraster")
     assert sorted(ABI.structs) == sorted(list(_native.STRUCTS) + ["gsr_png_piece", "gsr_png_file"])
     assert {k: v for k, v in ABI.constants.items() if k.startswith("GSR_ERR") or k in ("GSR_OK", "GSR_NEED_CAPACITY")} == {
@@ -121,9 +121,10 @@ def test_header_binding_and_library_agree(native_lib, name):
     fn = getattr(native_lib, name)
     assert fn.argtypes is not None and len(fn.argtypes) == len(params)
     scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
-               "long long": ctypes.c_longlong, "uint64_t": ctypes.c_uint64}  # written again here: what the 80 declarations use
+               "long long": ctypes.c_longlong, "uint64_t": ctypes.c_uint64}  # written again here: what the 86 declarations use
     typed = {"gsr_stage1_result*": _native.Stage1Result, "const gsr_tuning*": _native.Tuning, "const gsr_adjust_copy*": _native.AdjustCopy,
-             "const gsr_adam_tensor*": _native.AdamTensor, "const gsr_frame_panel*": _native.FramePanel, "gsr_profile*": _native.Profile}
+             "const gsr_adam_tensor*": _native.AdamTensor, "const gsr_frame_panel*": _native.FramePanel, "gsr_profile*": _native.Profile,
+             "gsr_layout_piece*": _native.LayoutPiece}
     for got, (decl, pname, is_pointer, _) in zip(fn.argtypes, params):
         want = ctypes.POINTER(typed[decl]) if decl in typed else ctypes.c_void_p if is_pointer else scalars[decl]
         assert got is want, (pname, decl, got)
@@ -136,7 +137,7 @@ _DTYPES = {"gsr_png_piece": png_decode._PIECE, "gsr_png_file": png_decode._FILE}
 
 @pytest.mark.parametrize("name", list(ABI.structs))
 def test_struct_mirrors_follow_the_header(name):
-    """Field names, order, C types and array lengths of every hand-written mirror -- the six ctypes classes, the two numpy dtypes --
+    """Field names, order, C types and array lengths of every hand-written mirror -- the seven ctypes classes, the two numpy dtypes --
     equal the header's struct; with the natural alignment both sides use, the offsets follow."""
     fields = ABI.structs[name]
     if name in _DTYPES:

@@ -140,7 +140,7 @@ def test_the_scalars_are_the_doubles_rounded_once(t):
 def test_header_binding_and_library_have_the_step(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     assert hdr.functions["gsr_adam_step"][0] == "int" and "gsr_adam_step" in _native.EXPORTED_SYMBOLS and hasattr(native_lib, "gsr_adam_step")
     assert hdr.constants["GSR_ADAM_MAX_TENSORS"] == _native.ADAM_MAX_TENSORS == 32
     T = _native.AdamTensor

@@ -201,7 +201,7 @@ def test_new_symbols_in_header_binding_and_library(native_lib):
     assert ctypes.sizeof(_native.AdjustCopy) == 24
     assert [hdr.constants["GSR_ADJUST_" + m] for m in ("COPY", "CLAMP_TAIL", "OFFSET_STAT", "ANCHOR_STAT")] == [0, 1, 2, 3]
     assert (_native.ADJUST_COPY, _native.ADJUST_CLAMP_TAIL, _native.ADJUST_OFFSET_STAT, _native.ADJUST_ANCHOR_STAT) == (0, 1, 2, 3)
-    assert hdr.constants["GSR_ABI_VERSION"] == 8  # additions only
+    assert hdr.constants["GSR_ABI_VERSION"] == 9
 
 
 def test_native_argument_checks(native_lib):

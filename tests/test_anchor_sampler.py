@@ -265,7 +265,7 @@ def test_new_symbols_in_header_binding_and_library(native_lib):
         assert s in _abi.header().functions, s
         assert s in _native.EXPORTED_SYMBOLS, s
         assert hasattr(native_lib, s), s
-    assert native_lib.gsr_abi_version() == 8
+    assert native_lib.gsr_abi_version() == 9
     assert native_lib.gsr_anchor_sample_workspace_bytes(500_000, 2000) >= 2 * 500_000
     assert native_lib.gsr_anchor_sample_workspace_bytes(0, 2000) > 0 and native_lib.gsr_anchor_sample_workspace_bytes(-1, 2000) == 0
     # argument checks run before anything touches a device

@@ -208,7 +208,7 @@ def test_new_symbols_in_header_binding_and_library(native_lib):
         assert s in _abi.header().functions, s
         assert s in _native.EXPORTED_SYMBOLS, s
         assert hasattr(native_lib, s), s
-    assert native_lib.gsr_abi_version() == 8
+    assert native_lib.gsr_abi_version() == 9
     assert native_lib.gsr_crossattn_workspace_bytes(1, 8, 2000, 2000) >= 8 * 4000 * 12
     assert native_lib.gsr_crossattn_workspace_bytes(1, 8, 0, 5) == 0
     # argument checks run before anything touches a device

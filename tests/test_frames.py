@@ -225,7 +225,7 @@ def test_the_colour_tables_are_what_matplotlib_gives():
 def test_header_binding_and_library_agree(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     assert hdr.constants["GSR_FRAME_MAX_PANELS"] == 8 and _native.FRAME_MAX_PANELS == 8 == Fr.MAX_PANELS
     for k, name in enumerate(("QUANT", "QUANT_CLAMP", "ABSDIFF", "NORMAL", "CMAP_CV", "CMAP_MPL_ALIGNED", "CMAP_MPL")):
         assert hdr.constants[f"GSR_FRAME_{name}"] == k and getattr(_native, f"FRAME_{name}") == k == getattr(Fr, name) == getattr(O, name)

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_library_exports_every_declared_symbol(native_lib):
     from gscream_amd import _abi, _native
     declared = set(_abi.header().functions)
-    assert len(declared) == 80 and declared == set(_native.EXPORTED_SYMBOLS), declared ^ set(_native.EXPORTED_SYMBOLS)
+    assert len(declared) == 86 and declared == set(_native.EXPORTED_SYMBOLS), declared ^ set(_native.EXPORTED_SYMBOLS)
     for sym in declared:
         assert hasattr(native_lib, sym), sym
     assert native_lib.gsr_version().startswith(b"gsraster")
@@ -30,7 +30,7 @@ def test_tuning_struct_layout_and_the_inference_twin():
     import ctypes
     from gscream_amd import _native, rasterizer as RZ
     assert ctypes.sizeof(_native.Tuning) == 40 and _native.Tuning.inference.offset == 12
-    assert _native.Tuning.walk_depths_valid.offset == 28 and _native.Tuning.walk_depths.offset == 32 and _native.ABI_VERSION == 8
+    assert _native.Tuning.walk_depths_valid.offset == 28 and _native.Tuning.walk_depths.offset == 32 and _native.ABI_VERSION == 9
     RZ.set_tuning(tile_cull=False, partial_sort=False)
     try:
         assert RZ._tuning_variants[(1, 0)].inference == 1 and RZ._tuning.inference == 0 and RZ._tuning_variants[(0, 1)].occlusion_cut == 1
@@ -52,14 +52,18 @@ def test_workspace_sizes(native_lib):
     assert 13 * R <= b <= 13 * R + 4096    # 8-B sort key + 4-B sorted id + 1 "slot written" byte per instance
     assert native_lib.gsr_backward_scratch_bytes(P, R) >= 48 * R
     assert native_lib.gsr_geom_bytes(0) > 0 and native_lib.gsr_binning_bytes(0) > 0
-    # layout mirror used by the tests agrees with the C carve
+    # the layout reader the tests decode with shows the pieces where the library's own query puts them
     from gscream_amd import _layout
     buf = torch.zeros(native_lib.gsr_image_bytes(5000, 112, 71), dtype=torch.uint8)
     v = _layout.image_views(buf, 5000, 112, 71)
     assert v["ranges"].shape == (35, 2) and v["table"].shape == (5, 35)  # 5 = ceil(5000 / 1024) binning chunks (gsr_num_chunks)
-    # the last field of the mirror ends inside the buffer the library asked for (the C carve and the mirror agree on every size)
-    last = v["tile_group"]
-    assert last.data_ptr() + last.numel() * 4 <= buf.data_ptr() + buf.numel()
+    # every view starts at its piece's reported offset and spans it; the last piece ends in the final 256 bytes of what the library
+    # asked for (tests/test_workspace_sizes.py walks the whole grid of sizes)
+    pieces = _layout._pieces("IMAGE", P=5000, W=112, H=71)
+    for k, t in v.items():
+        assert t.data_ptr() - buf.data_ptr() == pieces[k].offset and t.numel() * t.element_size() == pieces[k].count * pieces[k].elem_size, k
+    last = pieces["tile_group"]
+    assert last.offset == max(p.offset for p in pieces.values()) and 0 <= buf.numel() - (last.offset + last.count * last.elem_size) < 256
     assert _layout.num_chunks(1_000_000) == 256 and _layout.num_chunks(100_000) == 98 and _layout.num_chunks(1) == 1
 
 
@@ -222,10 +226,10 @@ def test_init_state_generator_follows_create_from_pcd():
 
 
 def test_segment_position_helpers_mirror_the_header():
-    """gscream_amd/_layout.py ckpt_pos = gsr_common.h gsr_ckpt_pos: seven segments of L, six of 3 L, then
+    """gscream_amd/_layout.py ckpt_pos asks the library's gsr_common.h gsr_ckpt_pos: seven segments of L, six of 3 L, then
     segments of 8 L (round 6), all at FIXED list positions (they must not follow the list length: the occlusion cut-off shortens lists
     behind everything that blends, and moving boundaries would re-associate the forward's sums), then the rest.  (The GPU kernels and
-    this mirror are compared through the checkpoints in test_second_tier_of_depth_segments.)"""
+    these positions are compared through the checkpoints in test_second_tier_of_depth_segments.)"""
     from gscream_amd import _layout as LY
     assert LY.SEG_MAX == LY.SEG1 + LY.SEG2 == 27
     for L in (64, 128):
@@ -245,7 +249,7 @@ def test_C_stub_module_imports_and_exports_the_five_entry_points():
 
 
 def test_tile_to_xcd_map_and_view_cache():
-    """Round 5: (1) chunks of four consecutive tiles dealt round-robin to the XCDs (gsr_common.h gsr_xcd_tile, mirrored in _layout): every
+    """Round 5: (1) chunks of four consecutive tiles dealt round-robin to the XCDs (gsr_common.h gsr_xcd_tile, asked through _layout): every
     tile is some XCD's slot exactly once, for image sizes with and without a remainder.  (2) the per-view walk-depth cache of the mirror:
     keyed by the view matrix's address + image size, first visit records (valid 0), later visits order (valid 1), least recently used
     out first, off on request."""

@@ -215,7 +215,7 @@ def test_native_declarations(native_lib):
     from tests import arena_helpers as A
     from gscream_amd import _abi, _native
     constants = _abi.header().constants
-    assert constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     table = A.header_table()
     for name in ("gsr_jpeg_capacity", "gsr_jpeg_workspace_bytes", "gsr_jpeg_encode"):
         assert name in table and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)

@@ -216,7 +216,7 @@ def test_header_binding_and_library_agree(native_lib):
     writable = [p[1] for p in table["gsr_lpips"] if p[2] and not p[3]]
     assert writable == ["workspace", "out_plain", "out_layers", "out_masked", "out_spatial", "stream"]
     assert [p[1] for p in table["gsr_conv3x3_relu"] if p[2] and not p[3]] == ["out", "stream"]
-    assert hdr.constants["GSR_ABI_VERSION"] == 8, "new exports do not change the ABI version"
+    assert hdr.constants["GSR_ABI_VERSION"] == 9
 
 
 def test_argument_checks_without_a_gpu(native_lib):

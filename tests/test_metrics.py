@@ -274,7 +274,7 @@ def test_fp32_is_the_references_arithmetic():
 def test_header_binding_and_library_have_the_two_calls(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     assert hdr.constants["GSR_METRICS_CLAMP"] == 1 and hdr.constants["GSR_METRICS_QUANTIZE"] == 2
     assert hdr.functions["gsr_image_metrics_workspace_bytes"][0] == "size_t" and hdr.functions["gsr_image_metrics"][0] == "int"
     for name in ("gsr_image_metrics_workspace_bytes", "gsr_image_metrics"):

@@ -168,7 +168,7 @@ def test_other_sizes_and_bad_arguments_on_the_torch_path():
 def test_header_binding_and_library_have_the_two_calls(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     for name in ("gsr_depth_points", "gsr_point_normals"):
         assert hdr.functions[name][0] == "int" and name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)
     assert len(native_lib.gsr_depth_points.argtypes) == 7 and len(native_lib.gsr_point_normals.argtypes) == 8

@@ -128,7 +128,7 @@ def test_capacity_formula_against_noise(native_lib):
 def test_abi_header_and_symbol_list(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and _native.ABI_VERSION == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and _native.ABI_VERSION == 9 and native_lib.gsr_abi_version() == 9
     assert hdr.functions["gsr_png_encode"][0] == "int"
     for name in ("gsr_png_capacity", "gsr_png_workspace_bytes"):
         assert hdr.functions[name][0] == "size_t"

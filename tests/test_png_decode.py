@@ -161,7 +161,7 @@ def test_read_images_and_evaluate_files_on_the_host(tmp_path):
 def test_abi_entries(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and native_lib.gsr_abi_version() == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and native_lib.gsr_abi_version() == 9
     assert hdr.functions["gsr_png_decode"][0] == "int" and hdr.functions["gsr_png_decode_workspace_bytes"][0] == "size_t"
     for name in ("gsr_png_decode_workspace_bytes", "gsr_png_decode"):
         assert name in _native.EXPORTED_SYMBOLS and hasattr(native_lib, name)

@@ -210,7 +210,7 @@ def test_resize_pil_image_routes_by_mode(monkeypatch):
 def test_abi_entries(native_lib):
     from gscream_amd import _abi, _native
     hdr = _abi.header()
-    assert hdr.constants["GSR_ABI_VERSION"] == 8 and native_lib.gsr_abi_version() == 8 and _native.ABI_VERSION == 8
+    assert hdr.constants["GSR_ABI_VERSION"] == 9 and native_lib.gsr_abi_version() == 9 and _native.ABI_VERSION == 9
     table = A.header_table()
     names = ("gsr_resize_u8", "gsr_resize_f32", "gsr_resize_nearest_u8", "gsr_resize_nearest_f32")
     for name in names:
