@@ -18,6 +18,8 @@
 //              range limit, 8 samples per thread as one 8-byte store into the component's plane.  Mirrors jpeg.hip's `transform`.
 //   colour   : a thread per four pixels of a row: chroma upsampling (rule 5) from the planes, conversion (rule 6), the HWC store, in
 //              dwords where the four pixels are whole and aligned.
+// The entropy kernel has a second entry behind a per-interval predicate (`only`): gsr_jpeg_decode launches the plain one, all intervals; the split decode
+// of jpeg_split.hip runs this file's launcher (jpeg_decode_launch.h) with its own launches between markers and entropy and names the intervals left here.
 // idct and colour run a grid of (G, nfiles) with a stride loop inside the file; G comes from the call's averages (the host knows no
 // file's size: the tables are device memory).  Integer arithmetic only.
 #include <hip/hip_runtime.h>
@@ -26,6 +28,7 @@
 #include "gsr_api.h"
 #include "gsr_carve.h"
 #include "gsr_scan.h"
+#include "jpeg_decode_launch.h"
 #include "jpeg_entropy.h"
 
 static_assert(sizeof(gsr_jpeg_file) == 104, "the file table's layout");
@@ -39,12 +42,6 @@ static_assert(JPGE_OK == GSR_JPEG_DECODE_OK && JPGE_TRUNCATED == GSR_JPEG_DECODE
 #define JD_IDCT_BLOCKS 32  // blocks per round of a 256-thread idct workgroup
 #define JD_LDS_ROW 72      // dwords between two blocks in the idct's LDS tiles
 
-struct JdWorkspace {
-    uint8_t* area;
-    unsigned long long area_bytes;
-    uint32_t *ivl_start, *ivl_end;
-    int32_t *ivl_status, *ivl_owner;
-};
 // The caller's area of `area_bytes` (rounded up to 16), then per interval {start, end, status, owner}.  The launcher puts the tables at
 // the END of what the caller gave: its area is whatever lies in front of them.
 struct JdCarve {
@@ -64,25 +61,7 @@ static JdCarve jd_carve(void* base, size_t area_bytes, int nintervals)
     r.bytes = c.total();
     return r;
 }
-static size_t jd_tables_bytes(int nintervals) { return jd_carve(nullptr, 0, nintervals).bytes; }  // the tables' part alone: the least workspace a call is taken with
-
-// what the sizes and the sampling of a file make
-struct JdGeometry {
-    uint32_t mcux, mcuy, mcus, blocks, per;  // per: MCUs in an interval (all of them without DRI)
-    int ny, bpm;                             // component 0's blocks per MCU, all blocks per MCU
-};
-__device__ __forceinline__ JdGeometry jd_geometry(const gsr_jpeg_file& f)  // of a validated file
-{
-    JdGeometry g;
-    g.mcux = ((uint32_t)f.W + 8u * f.hs - 1u) / (8u * f.hs);
-    g.mcuy = ((uint32_t)f.H + 8u * f.vs - 1u) / (8u * f.vs);
-    g.mcus = g.mcux * g.mcuy;  // <= 8192^2
-    g.ny = f.hs * f.vs;
-    g.bpm = g.ny + f.C - 1;
-    g.blocks = g.mcus * (uint32_t)g.bpm;  // < 2^29
-    g.per = f.restart_interval ? (uint32_t)f.restart_interval : g.mcus;
-    return g;
-}
+size_t jd_tables_bytes(int nintervals) { return jd_carve(nullptr, 0, nintervals).bytes; }  // the tables' part alone: the least workspace a call is taken with
 
 // ---- validate ----
 __global__ void __launch_bounds__(64) jpeg_decode_validate_kernel(const gsr_jpeg_file* __restrict__ files, int nintervals, unsigned long long nbytes,
@@ -221,8 +200,8 @@ struct JdSink {
     }
 };
 
-__global__ void __launch_bounds__(64) jpeg_decode_entropy_kernel(const uint8_t* __restrict__ bytes, const gsr_jpeg_file* __restrict__ files, int nfiles,
-                                                                 const JpgeHuffman* __restrict__ huffman, JdWorkspace ws, const int32_t* status)
+__device__ __forceinline__ void jd_entropy_interval(const uint8_t* __restrict__ bytes, const gsr_jpeg_file* __restrict__ files, int nfiles,
+                                                    const JpgeHuffman* __restrict__ huffman, JdWorkspace ws, const int32_t* status)
 {
     __shared__ JpgeCode codes[6];
     const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
@@ -254,6 +233,20 @@ __global__ void __launch_bounds__(64) jpeg_decode_entropy_kernel(const uint8_t* 
         rc = jpge_interval(in, start, end, k + 1u < (uint32_t)fl.intervals, use, g.ny, g.bpm, first_mcu, min(g.per, g.mcus - first_mcu), sink);
     }
     if (lane == 0) ws.ivl_status[i] = rc;
+}
+__global__ void __launch_bounds__(64) jpeg_decode_entropy_kernel(const uint8_t* __restrict__ bytes, const gsr_jpeg_file* __restrict__ files, int nfiles,
+                                                                 const JpgeHuffman* __restrict__ huffman, JdWorkspace ws, const int32_t* status)
+{
+    jd_entropy_interval(bytes, files, nfiles, huffman, ws, status);
+}
+// The same kernel behind a per-interval predicate, for the split decode (jpeg_split.hip): only[i] != 0: interval i is this kernel's; the
+// workgroup of any other interval reads the word and leaves.  (A kernel of its own: the one above is compiled as it was.)
+__global__ void __launch_bounds__(64) jpeg_decode_entropy_only_kernel(const uint8_t* __restrict__ bytes, const gsr_jpeg_file* __restrict__ files, int nfiles,
+                                                                      const JpgeHuffman* __restrict__ huffman, JdWorkspace ws, const int32_t* status,
+                                                                      const int32_t* __restrict__ only)
+{
+    if (!only[blockIdx.x]) return;
+    jd_entropy_interval(bytes, files, nfiles, huffman, ws, status);
 }
 
 // ---- status ----
@@ -425,9 +418,9 @@ __global__ void __launch_bounds__(256) jpeg_decode_colour_kernel(const gsr_jpeg_
     }
 }
 
-static hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
-                                     const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
-                                     size_t workspace_bytes, hipStream_t stream)
+hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const gsr_jpeg_file* files, int nfiles, int nintervals, const uint16_t* quant, int nquant,
+                              const gsr_jpeg_huffman* huffman, int nhuffman, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
+                              size_t workspace_bytes, hipStream_t stream, const JdBetween* between)
 {
     const size_t tables = jd_tables_bytes(nintervals);
     if (workspace_bytes < tables) return hipErrorInvalidValue;
@@ -438,8 +431,13 @@ static hipError_t jpeg_launch_decode(const uint8_t* bytes, size_t nbytes, const 
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(jpeg_decode_markers_kernel, dim3((uint32_t)nfiles), dim3(JD_MARK_THREADS), 0, stream, bytes, files, ws, status);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((uint32_t)nintervals), dim3(64), 0, stream, bytes, files, nfiles, (const JpgeHuffman*)huffman, ws,
-                       (const int32_t*)status);
+    if (between && (e = between->launch(between->self, ws, stream)) != hipSuccess) return e;
+    if (between)
+        hipLaunchKernelGGL(jpeg_decode_entropy_only_kernel, dim3((uint32_t)nintervals), dim3(64), 0, stream, bytes, files, nfiles, (const JpgeHuffman*)huffman,
+                           ws, (const int32_t*)status, between->only);
+    else
+        hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((uint32_t)nintervals), dim3(64), 0, stream, bytes, files, nfiles, (const JpgeHuffman*)huffman, ws,
+                           (const int32_t*)status);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(jpeg_decode_status_kernel, dim3((uint32_t)((nfiles + 63) / 64)), dim3(64), 0, stream, files, nfiles, ws, status);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -476,7 +474,7 @@ extern "C" int gsr_jpeg_decode(const uint8_t* bytes, size_t nbytes, const gsr_jp
     if (workspace_bytes < jd_tables_bytes(nintervals))
         return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "jpeg decode: workspace_bytes=%zu is below the tables' part alone", workspace_bytes);
     GSR_HIP(jpeg_launch_decode(bytes, nbytes, files, nfiles, nintervals, quant, nquant, huffman, nhuffman, out, out_bytes, status, workspace,
-                               workspace_bytes, (hipStream_t)stream),
+                               workspace_bytes, (hipStream_t)stream, nullptr),
             "jpeg decode");
     return GSR_OK;
 }

@@ -15,8 +15,9 @@ found there, and Huffman decoding, dequantisation, the IDCT, chroma upsampling a
 (gscream_amd/csrc/jpeg_decode.hip, `last_path = "hip"`), all files of a call in one launch sequence, with no synchronisation: the
 sizes come from SOF0.  The unit of parallel work is the restart interval, one wavefront each.  Every file `jpeg.encode` writes has an
 interval per MCU row.  A file without restart markers -- what PIL and most cameras write -- is ONE interval: one wavefront walks its
-whole scan, which is correct and slow: 233 ms for one 567x1008 file against PIL's 3 ms (INTEGRATION Z has the numbers; `read`'s
-docstring says which files to bring here).
+whole scan, which is correct and slow: 232.1 ms for one 567x1008 file against PIL's 2.8 ms.  `split="auto"` / "always" cut such an interval
+into subsequences of 128 bytes, a lane each (gscream_amd/csrc/jpeg_split.hip, include/gsraster_jpeg_split.h): 6.7 ms for that file, 13.7 ms
+for 80 of them (INTEGRATION Z has the numbers; `read`'s docstring says which files to bring here).
 The picture is PIL's (libjpeg-turbo: islow IDCT, fancy upsampling) byte for byte; the rules and the status codes are in
 include/gsraster_jpeg_decode.h in full.
 
@@ -46,6 +47,16 @@ last_info = {}    # filled by check / read: files, intervals, host_decoded
 HEADER = "gsraster_jpeg_decode.h"
 _ABI = _abi.extension(HEADER)  # the family's own header: its functions are typed from it, its structs and codes read from it
 EXPORTED_SYMBOLS = tuple(_ABI.functions)
+SPLIT_HEADER = "gsraster_jpeg_split.h"  # the split decode: a family of its own beside this one, the same library
+_SPLIT_ABI = _abi.extension(SPLIT_HEADER)
+SPLIT_EXPORTED_SYMBOLS = tuple(_SPLIT_ABI.functions)
+SPLITS = ("never", "auto", "always")
+# The shipped defaults (INTEGRATION Z, profiles/jpeg_decode_timing.json): 128 = the best median of the subsequence_bytes sweep on 80 marker-less
+# files; 4644 = the smallest measured interval length from which the split path stays below the one-wave path; "never": the rule for "auto" is
+# not met to the letter, and existing tests pin a default call's last_info.
+DEFAULT_SUBSEQUENCE_BYTES = 128
+DEFAULT_MIN_BYTES = 4644
+DEFAULT_SPLIT = "never"
 STATUS = tuple(name[len("GSR_JPEG_DECODE_"):] for name, _ in sorted(((n, v) for n, v in _ABI.constants.items() if n.startswith("GSR_JPEG_DECODE_")),
                                                                     key=lambda item: item[1]))
 _NUMPY = {"uint8_t": "u1", "uint16_t": "<u2", "int32_t": "<i4", "uint32_t": "<u4", "uint64_t": "<u8"}
@@ -59,20 +70,32 @@ _FILE, _HUFFMAN = _dtype("gsr_jpeg_file"), _dtype("gsr_jpeg_huffman")
 assert _FILE.itemsize == 104 and _HUFFMAN.itemsize == 272
 _ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43,
            36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)  # natural index of coding position k
-_lib = None
+_lib = _split_lib = None
+
+
+def _typed(lib, abi):
+    for name, (returns, params) in abi.functions.items():
+        fn = getattr(lib, name)  # AttributeError: a library built without the family's object file
+        fn.restype = _abi.ctype(returns, returns=True)
+        fn.argtypes = [_abi.ctype(ctype) for ctype, _, _, _ in params]
+    return lib
 
 
 def _library():
     """libgsraster.so with this family's functions typed from their declarations (_abi.ctype: an unknown type raises)."""
     global _lib
     if _lib is None:
-        lib = _native.load()
-        for name, (returns, params) in _ABI.functions.items():
-            fn = getattr(lib, name)  # AttributeError: a library built without jpeg_decode.o
-            fn.restype = _abi.ctype(returns, returns=True)
-            fn.argtypes = [_abi.ctype(ctype) for ctype, _, _, _ in params]
-        _lib = lib
+        _lib = _typed(_native.load(), _ABI)
     return _lib
+
+
+def _split_library():
+    """The same library with the split family's functions typed as well, on the first split decode: a library without them (one
+    built from a commit before the family) still serves split="never", and raises AttributeError here."""
+    global _split_lib
+    if _split_lib is None:
+        _split_lib = _typed(_library(), _SPLIT_ABI)
+    return _split_lib
 
 
 def status_name(code):
@@ -109,12 +132,19 @@ class Parsed(NamedTuple):
 
 class JpegPictures(NamedTuple):
     """images: uint8 [H, W, C] views of one buffer, one per file; status: int32 [n] on the device (GSR_JPEG_DECODE_* codes, 0 = OK);
-    decoded: int32 [n] on the device, the intervals decoded; intervals: per file, from the host parser; names: what `check` calls the files."""
+    decoded: int32 [n] on the device, the intervals decoded; intervals: per file, from the host parser; names: what `check` calls the files.
+    From a split decode also info: int32 [n, 4] on the device, per file {intervals split, intervals repaired, subsequences, chunks};
+    words: the one int32 buffer that holds status and info (what `check` reads back); trace: None, or with decode(trace=True) int32
+    [rows, 5] on the device, per subsequence (bit, j, k, first_block, blocks) -- the split intervals in order, each one's subsequences
+    in order, sum(info[:, 2]) rows used."""
     images: List[torch.Tensor]
     status: torch.Tensor
     decoded: torch.Tensor
     intervals: tuple = ()
     names: tuple = ()
+    info: torch.Tensor = None
+    words: torch.Tensor = None
+    trace: torch.Tensor = None
 
 
 _SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential", 0xC6: "differential progressive",
@@ -256,12 +286,25 @@ def _pil_picture(data):
     return np.array(a.reshape(a.shape[0], a.shape[1], -1))  # (a copy: PIL's buffer is read-only)
 
 
-def decode(files, device, names=None):
+def decode(files, device, names=None, split=DEFAULT_SPLIT, subsequence_bytes=None, min_bytes=None, trace=False):
     """files: a list of bytes-like objects, one JPEG file each, of any sizes, samplings and writers -> JpegPictures on `device`.  One
     H2D copy of one staging buffer (tables and bytes), one launch sequence on torch's current stream, no synchronisation and nothing
     read back: call `check` for that.  Raises ValueError (from `parse`) before anything is launched when a file is outside the accepted
-    subset."""
+    subset.
+    split: "never" -- gsr_jpeg_decode, a wavefront per restart interval; "always" -- gsr_jpeg_decode_split with every interval of at
+    least two subsequences cut into subsequences of `subsequence_bytes` (a power of two, 16 .. 1024) and decoded a lane per
+    subsequence (include/gsraster_jpeg_split.h); "auto" -- the same for the intervals of at least `min_bytes`, the others as under
+    "never".  The pictures and the status codes are the same bytes under all three.  trace=True (split decodes only) also returns the
+    per-subsequence entry states and counts.  The CPU path ignores all four."""
     global last_path
+    if split not in SPLITS:
+        raise ValueError(f"jpeg_decode: split={split!r} (have {', '.join(repr(v) for v in SPLITS)})")
+    B = DEFAULT_SUBSEQUENCE_BYTES if subsequence_bytes is None else subsequence_bytes
+    if not isinstance(B, int) or isinstance(B, bool) or not 16 <= B <= 1024 or B & (B - 1):
+        raise ValueError(f"jpeg_decode: subsequence_bytes={subsequence_bytes!r} (need a power of two from 16 to 1024)")
+    least = (0 if split == "always" else DEFAULT_MIN_BYTES) if min_bytes is None else min_bytes
+    if not isinstance(least, int) or isinstance(least, bool) or not 0 <= least < 1 << 31:
+        raise ValueError(f"jpeg_decode: min_bytes={min_bytes!r} (need an integer from 0 to 2^31 - 1)")
     device = torch.device(device)
     files = list(files)
     if not files:
@@ -317,46 +360,71 @@ def decode(files, device, names=None):
     with torch.cuda.device(device):
         dev = staging.to(device, non_blocking=True)
         out = _device_bytes(max(out_at, 16), device, "out")
-        status = _device_bytes(8 * nfiles, device, "status").view(torch.int32).view(nfiles, 2)
-        ws_bytes = int(lib.gsr_jpeg_decode_workspace_bytes(area_at, nfiles, nintervals))
-        if ws_bytes == 0:
-            raise ValueError("jpeg_decode: the call's coefficients and planes are beyond 2^40 bytes")
-        workspace = _device_bytes(ws_bytes, device, "workspace")
         base = dev.data_ptr()
-        _native.run("gsr_jpeg_decode", out.device, ctypes.c_void_p(base + off_bytes), nbytes, ctypes.c_void_p(base), nfiles, nintervals,
-                    ctypes.c_void_p(base + off_quant), len(qindex), ctypes.c_void_p(base + off_huff), len(hindex), _native.ptr(out), out.numel(),
-                    _native.ptr(status), _native.ptr(workspace), ws_bytes)
+        args = (ctypes.c_void_p(base + off_bytes), nbytes, ctypes.c_void_p(base), nfiles, nintervals, ctypes.c_void_p(base + off_quant), len(qindex),
+                ctypes.c_void_p(base + off_huff), len(hindex), _native.ptr(out), out.numel())
+        if split == "never":  # today's call, untouched
+            words = info = rows = None
+            status = _device_bytes(8 * nfiles, device, "status").view(torch.int32).view(nfiles, 2)
+            ws_bytes = int(lib.gsr_jpeg_decode_workspace_bytes(area_at, nfiles, nintervals))
+            if ws_bytes == 0:
+                raise ValueError("jpeg_decode: the call's coefficients and planes are beyond 2^40 bytes")
+            workspace = _device_bytes(ws_bytes, device, "workspace")
+            _native.run("gsr_jpeg_decode", out.device, *args, _native.ptr(status), _native.ptr(workspace), ws_bytes)
+        else:
+            words = _device_bytes(24 * nfiles, device, "status").view(torch.int32)  # status {code, decoded} per file, then info: four per file
+            status, info = words[:2 * nfiles].view(nfiles, 2), words[2 * nfiles:].view(nfiles, 4)
+            ws_bytes = int(_split_library().gsr_jpeg_split_workspace_bytes(area_at, nfiles, nintervals, nbytes, B))
+            if ws_bytes == 0:
+                raise ValueError("jpeg_decode: the call's coefficients and planes are beyond 2^40 bytes")
+            workspace = _device_bytes(ws_bytes, device, "workspace")
+            rows = _device_bytes(20 * (nbytes // B + nintervals), device, "trace").view(torch.int32).view(-1, 5) if trace else None
+            _native.run("gsr_jpeg_decode_split", out.device, *args, _native.ptr(status), _native.ptr(workspace), ws_bytes, B, least,
+                        _native.ptr(rows) if trace else None, _native.ptr(info))
     images = []
     for i, p in enumerate(parsed):
         o = int(ftab["out_offset"][i])
         images.append(out[o:o + p.H * p.W * p.C].view(p.H, p.W, p.C))
-    return JpegPictures(images, status[:, 0], status[:, 1], counts, names)
+    return JpegPictures(images, status[:, 0], status[:, 1], counts, names, info, words, rows)
 
 
 def check(pictures, host_decoded=0):
-    """The one read-back: the status words of a decode.  Raises JpegDecodeError (index and code of every failed file) and fills
-    last_info: files, intervals, host_decoded."""
+    """The one read-back: the status words of a decode (with a split decode's counts in the same buffer).  Raises JpegDecodeError
+    (index and code of every failed file) and fills last_info: files, intervals, host_decoded, and after a split decode on the device
+    (decode's `split` other than "never") also split_intervals, repaired_intervals, subsequences."""
     global last_info
-    codes = pictures.status.cpu().numpy() if pictures.status.is_cuda else pictures.status.numpy()  # one copy
+    counts = None
+    if pictures.words is not None:
+        words = pictures.words.cpu().numpy()  # one copy
+        n = words.shape[0] // 6
+        codes, counts = words[:2 * n].reshape(n, 2)[:, 0], words[2 * n:].reshape(n, 4)
+    else:
+        codes = pictures.status.cpu().numpy() if pictures.status.is_cuda else pictures.status.numpy()  # one copy
     last_info = {"files": int(codes.shape[0]) + host_decoded, "intervals": int(sum(pictures.intervals)), "host_decoded": host_decoded}
+    if counts is not None:
+        last_info.update(split_intervals=int(counts[:, 0].sum()), repaired_intervals=int(counts[:, 1].sum()), subsequences=int(counts[:, 2].sum()))
     failures = [(int(i), int(codes[i])) for i in np.flatnonzero(codes)]
     if failures:
         raise JpegDecodeError(failures, pictures.names)
     return pictures
 
 
-def read(paths, device, unsupported="raise"):
+def read(paths, device, unsupported="raise", split=DEFAULT_SPLIT):
     """Read the files, decode them in one call and check -> the list of uint8 [H, W, C] pictures, in the order of `paths`.
     unsupported="pil": the files `parse` rejects (progressive, CMYK, ...) go through PIL on the host and are uploaded; last_info counts
     them as host_decoded.  That is never the default: by default such a file raises ValueError.
-    What it is worth, measured at 567x1008x3 (tools/jpeg_decode_bench.py, INTEGRATION Z): a batch of files with restart markers
-    (gscream_amd.jpeg's, the frames of video.MjpegWriter) is where this call belongs -- 80 of them in 27 ms against 385 ms of
-    Image.open + upload.  It LOSES to PIL's loop on files without markers (80 PIL-written files: 240 ms against 224 ms; one: 233 ms
-    against 3.2 ms -- one wavefront walks the whole scan) and on a single file of either kind (6.8 ms against 4.6 ms): read those
-    with PIL."""
+    split: decode's -- "never" (the default), "auto", "always".
+    What it is worth, measured at 567x1008x3 (tools/jpeg_decode_bench.py, INTEGRATION Z; decode + check against Image.open + upload):
+    80 files with restart markers (gscream_amd.jpeg's, the frames of video.MjpegWriter): 22.5 ms, 17.7 ms with split="auto", PIL
+    361.4 ms.  80 files without markers (PIL's, a camera's): 238.9 ms by default -- one wavefront walks a whole scan -- and
+    13.7 ms with split="auto", PIL 214.1 ms: pass split="auto" for such files.  One file with markers: 6.81 ms, 2.59 ms with
+    split="auto", PIL 4.80 ms.  One file without markers STILL LOSES to PIL: 6.67 ms with split="auto" (232.1 ms without)
+    against 2.80 ms -- read a single PIL- or camera-written file with PIL.  The default stays "never" (INTEGRATION Z says why)."""
     global last_info
     if unsupported not in ("raise", "pil"):
         raise ValueError(f"jpeg_decode: unsupported={unsupported!r} (have 'raise', 'pil')")
+    if split not in SPLITS:
+        raise ValueError(f"jpeg_decode: split={split!r} (have {', '.join(repr(v) for v in SPLITS)})")
     paths = [os.fspath(p) for p in paths]
     blobs = []
     for path in paths:
@@ -375,7 +443,7 @@ def read(paths, device, unsupported="raise"):
                 images[i] = torch.from_numpy(_pil_picture(data)).to(device)
     hosted = len(paths) - len(mine)
     if mine:
-        pictures = check(decode([blobs[i] for i in mine], device, [paths[i] for i in mine]), host_decoded=hosted)
+        pictures = check(decode([blobs[i] for i in mine], device, [paths[i] for i in mine], split=split), host_decoded=hosted)
         for i, image in zip(mine, pictures.images):
             images[i] = image
     else:

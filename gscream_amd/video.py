@@ -172,13 +172,14 @@ class MjpegReader:
         off, n = self.chunks[i]
         return self.data[off:off + n]
 
-    def frames(self, device, batch=8):
+    def frames(self, device, batch=8, split=None):
         from . import jpeg_decode
+        split = jpeg_decode.DEFAULT_SPLIT if split is None else split  # (jpeg_decode.decode's `split`, passed through)
         if batch < 1:
             raise ValueError(f"MjpegReader: batch={batch!r} (need >= 1)")
         for at in range(0, len(self.chunks), batch):
             ids = range(at, min(at + batch, len(self.chunks)))
-            pictures = jpeg_decode.check(jpeg_decode.decode([self.frame_bytes(i) for i in ids], device, [f"{self.path} frame {i}" for i in ids]))
+            pictures = jpeg_decode.check(jpeg_decode.decode([self.frame_bytes(i) for i in ids], device, [f"{self.path} frame {i}" for i in ids], split=split))
             for image in pictures.images:
                 if tuple(image.shape) != (self.H, self.W, 3):
                     raise ValueError(f"MjpegReader: {self.path}: a frame of {tuple(image.shape)} in a {self.H} x {self.W} stream")
