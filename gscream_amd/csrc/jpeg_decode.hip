@@ -157,32 +157,22 @@ __global__ void __launch_bounds__(JD_MARK_THREADS) jpeg_decode_markers_kernel(co
 }
 
 // ---- entropy ----
-struct JdTeam {
-    int lane, lanes;
-    __device__ void sync() { __syncthreads(); }
-};
 // byte `at` of the scan; every lane asks for the same byte.  The wave holds a window of JD_WINDOW bytes in one register per lane (lane l:
 // the dword at aligned + base + 4 l), filled by one coalesced load, and a byte comes out of it with v_readlane: no LDS word, no barrier.
 // (Measured against a 512-byte LDS window behind two barriers: the entropy launch 2 to 4 % shorter, 6.39 -> 6.25 ms for one 567x1008
 // file of 71 intervals.  The bytes are not what the wave waits for: it is one instruction stream per interval, a few hundred dependent
 // scalar instructions a symbol.)
 struct JdFetch {
-    const uint8_t* aligned;  // the scan's first byte, rounded down to a dword of `bytes`
-    uint32_t shift, limit;   // the scan starts at aligned + shift and ends at aligned + limit
-    uint32_t base;           // 0xffffffff = nothing loaded
+    JdScan scan;
+    uint32_t base;  // 0xffffffff = nothing loaded
     uint32_t mine;
     int lane;
     __device__ uint8_t operator()(uint32_t at)
     {
-        const uint32_t q = at + shift;
+        const uint32_t q = at + scan.shift;
         if (base == 0xffffffffu || q - base >= JD_WINDOW) {
             base = q & ~3u;
-            const uint32_t o = base + 4u * (uint32_t)lane;
-            uint32_t v = 0;
-            if (o < limit && limit - o >= 4u) v = *(const uint32_t*)(aligned + o);
-            else
-                for (uint32_t j = 0; j < 4u && o < limit && j < limit - o; j++) v |= (uint32_t)aligned[o + j] << (8u * j);
-            mine = v;
+            mine = scan.dword(base + 4u * (uint32_t)lane);
         }
         const uint32_t d = JPGE_UNIFORM(q - base);  // < JD_WINDOW
         return (uint8_t)((uint32_t)__builtin_amdgcn_readlane((int)mine, (int)(d >> 2)) >> (8u * (d & 3u)));
@@ -205,32 +195,19 @@ __device__ __forceinline__ void jd_entropy_interval(const uint8_t* __restrict__ 
 {
     __shared__ JpgeCode codes[6];
     const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-    const int f = (int)JPGE_UNIFORM(ws.ivl_owner[i]);
-    if ((uint32_t)f >= (uint32_t)nfiles || status[2 * f] != GSR_JPEG_DECODE_OK) return;
+    const int f = (int)JPGE_UNIFORM(jd_owner(i, files, nfiles, ws, status));  // (the lanes hold one state: the scalar registers' from here on)
+    if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
-    if (i < fl.first_interval || i >= fl.first_interval + fl.intervals) return;  // (an entry no sound file owns)
     const JdGeometry g = jd_geometry(fl);
-    const uint32_t k = (uint32_t)(i - fl.first_interval), first_mcu = k * g.per;
-    JdTeam tm = {lane, 64};
-    const JpgeCode* use[6] = {};
-    bool sound = true;
-    for (int c = 0; c < fl.C; c++) {
-        // a table two components share is built once
-        const bool dc_again = c > 0 && fl.dc[c] == fl.dc[c - 1], ac_again = c > 0 && fl.ac[c] == fl.ac[c - 1];
-        if (dc_again) use[2 * c] = use[2 * c - 2];
-        else { sound = jpge_build(tm, codes[2 * c], huffman + fl.dc[c]) && sound; use[2 * c] = &codes[2 * c]; }
-        if (ac_again) use[2 * c + 1] = use[2 * c - 1];
-        else { sound = jpge_build(tm, codes[2 * c + 1], huffman + fl.ac[c]) && sound; use[2 * c + 1] = &codes[2 * c + 1]; }
-    }
+    uint32_t slots;
     int rc = JPGE_TABLE;
-    if (sound) {
-        const uint8_t* scan = bytes + fl.scan_offset;
-        const uint32_t shift = (uint32_t)((uintptr_t)scan & 3u);
-        JdFetch in = {scan - shift, shift, shift + fl.scan_length, 0xffffffffu, 0u, lane};
+    if (jd_build(JdTeam{lane, 64}, codes, fl, huffman, slots)) {
+        const JpgeCode* use[6];
+        for (int e = 0; e < 6; e++) use[e] = &codes[(slots >> (4 * e)) & 7u];
+        JdFetch in = {jd_scan(bytes, fl), 0xffffffffu, 0u, lane};
         JdSink sink = {(int16_t*)(ws.area + fl.coef_offset), lane, jpge_natural(lane), 0};
-        // [start, end) lies in the scan: the markers kernel wrote positions of bytes it read
-        const uint32_t start = min(JPGE_UNIFORM(ws.ivl_start[i]), fl.scan_length), end = min(JPGE_UNIFORM(ws.ivl_end[i]), fl.scan_length);
-        rc = jpge_interval(in, start, end, k + 1u < (uint32_t)fl.intervals, use, g.ny, g.bpm, first_mcu, min(g.per, g.mcus - first_mcu), sink);
+        const JdPiece p = jd_piece(fl, g, i, ws);
+        rc = jpge_interval(in, JPGE_UNIFORM(p.start), JPGE_UNIFORM(p.end), !p.last, use, g.ny, g.bpm, p.first_mcu, p.mcus, sink);
     }
     if (lane == 0) ws.ivl_status[i] = rc;
 }

@@ -6,6 +6,8 @@
 //   Fetch   uint8_t operator()(uint32_t at)  byte `at` of the scan, at < the scan's length; every lane asks for the same byte
 //   Sink    put(k, v): coefficient at zigzag position k of the current block;  flush(block): the block is complete (all other
 //           coefficients are 0), store it as block number `block` of the file
+// The bit reader, the symbol and the value are written once for two modes (JPGE_WAVE / JPGE_LANE below): the interval loop here reads in
+// wave mode, the split decode of jpeg_split.h in lane mode; the rules of a block (component, DC size, AC step) are functions both call.
 // Every loop here consumes a bit or a coefficient, or ends at a fixed count; every table index is masked or checked.
 #pragma once
 #include <stdint.h>
@@ -101,49 +103,74 @@ JPGE_HD int jpge_marker_verdict(bool closed, uint32_t rst_found, bool numbered, 
     return (rst_found + 1u != intervals || !numbered) ? JPGE_RESTART : JPGE_OK;
 }
 
-// The bits of one interval: the bytes [pos, end) of the scan.  acc holds nbits bits, right-aligned, of which the last `fake` were
-// made up behind the end of the data (zeros); consuming one of them is an error.
-template <class Fetch>
+// How a reader keeps its words.  JPGE_WAVE: the team's lanes hold one state, every fetched byte and table word goes through JPGE_UNIFORM
+// (scalar registers), and the reader does not know where it stands.  JPGE_LANE: a lane has a state of its own (jpeg_split.h), nothing is
+// made uniform, and the reader tracks its position in the stuffed bytes (`pairs`, where()).
+enum { JPGE_WAVE = 0, JPGE_LANE = 1 };
+template <int Mode>
+JPGE_HD uint32_t jpge_word(uint32_t x) { return Mode == JPGE_WAVE ? JPGE_UNIFORM(x) : x; }
+
+// The bits of the scan from byte `start` on (JPGE_LANE: from its bit `bit`, 0 = the most significant), up to the interval's end.  acc holds
+// nbits bits, right-aligned, of which the last `fake` were made up behind the end of the data (zeros); consuming one of them is an
+// error.  Where the data ends, `end` comes down to `pos`: nothing more is taken, and `pos` stays what where() counts from.  `pairs`
+// (JPGE_LANE only; a constant 0 otherwise): bit i = the i-th last byte taken into acc was the FF of an FF 00 pair (two bytes of the scan).
+template <class Fetch, int Mode>
 struct JpgeReader {
     Fetch in;
     uint32_t pos, end;
     uint64_t acc;
+    uint32_t pairs;
     int nbits, fake;
-    JPGE_HD JpgeReader(const Fetch& f, uint32_t start, uint32_t stop) : in(f), pos(start), end(stop), acc(0), nbits(0), fake(0) {}
+    JPGE_HD JpgeReader(const Fetch& f, uint32_t start, uint32_t stop, int bit = 0) : in(f), pos(start), end(stop), acc(0), pairs(0), nbits(0), fake(0)
+    {
+        if (Mode == JPGE_LANE) {
+            refill();
+            nbits -= bit & 7;  // (nbits > 56)
+        }
+    }
     JPGE_HD void refill()  // -> nbits > 56; every round takes a byte of the data or makes one up
     {
         while (nbits <= 56) {
-            uint32_t b = 0;
+            uint32_t b = 0, pair = 0;
             bool have = false;
             if (pos < end) {
-                b = JPGE_UNIFORM(in(pos));
+                b = jpge_word<Mode>(in(pos));
                 if (b != 0xFFu) { pos++; have = true; }
-                else if (pos + 1 < end && JPGE_UNIFORM(in(pos + 1)) == 0u) { pos += 2; have = true; }
-                else pos = end;  // a fill byte, or the interval's last byte: the data ends here
+                else if (pos + 1 < end && jpge_word<Mode>(in(pos + 1)) == 0u) { pos += 2; have = true; pair = 1; }
+                else end = pos;  // a fill byte, or the interval's last byte: the data ends here
             }
             if (!have) { b = 0; fake += 8; }
             acc = (acc << 8) | b;
+            if (Mode == JPGE_LANE) pairs = (pairs << 1) | pair;
             nbits += 8;
         }
     }
     JPGE_HD uint32_t peek(int n) const { return (uint32_t)(acc >> (nbits - n)) & ((1u << n) - 1u); }  // n <= 16 <= nbits
     JPGE_HD bool drop(int n) { nbits -= n; return nbits >= fake; }                                       // false: made-up bits were used
     JPGE_HD int real() const { return nbits - fake; }
+    // JPGE_LANE: where the next bit lies; meaningful while no made-up bit has been used
+    JPGE_HD void where(uint32_t& byte, int& bit) const
+    {
+        const int held = (nbits + 7) >> 3, made = fake >> 3, live = held > made ? held - made : 0;  // bytes of acc not fully consumed; the made-up ones; the data's
+        const uint32_t twice = (uint32_t)__builtin_popcount((pairs >> made) & ((1u << live) - 1u));  // (live <= 8)
+        byte = pos - (uint32_t)live - twice;
+        bit = (8 - (nbits & 7)) & 7;
+    }
 };
 
-// the next symbol -> 0 .. 255, or -(status code)
-template <class Fetch>
-JPGE_HD int jpge_symbol(JpgeReader<Fetch>& r, const JpgeCode& code, int short_code)
+// the next symbol -> 0 .. 255, or -(status code): short_code where the data ended, else JPGE_BAD_CODE
+template <class Fetch, int Mode>
+JPGE_HD int jpge_symbol(JpgeReader<Fetch, Mode>& r, const JpgeCode& code, int short_code)
 {
     if (r.nbits < 32) r.refill();
     const uint32_t w = r.peek(16);
-    const uint32_t quick = JPGE_UNIFORM(code.look[w >> (16 - JPGE_LOOK_BITS)]);
+    const uint32_t quick = jpge_word<Mode>(code.look[w >> (16 - JPGE_LOOK_BITS)]);
     int n = (int)(quick >> 8), sym = (int)(quick & 255u);
     if (!n) {
         for (n = JPGE_LOOK_BITS + 1; n <= 16; n++) {
             const int32_t c = (int32_t)(w >> (16 - n));
-            if (c <= (int32_t)JPGE_UNIFORM(code.maxcode[n])) {
-                sym = (int)JPGE_UNIFORM(code.values[(uint32_t)(c + (int32_t)JPGE_UNIFORM(code.delta[n])) & 255u]);
+            if (c <= (int32_t)jpge_word<Mode>(code.maxcode[n])) {
+                sym = (int)jpge_word<Mode>(code.values[(uint32_t)(c + (int32_t)jpge_word<Mode>(code.delta[n])) & 255u]);
                 break;
             }
         }
@@ -153,14 +180,31 @@ JPGE_HD int jpge_symbol(JpgeReader<Fetch>& r, const JpgeCode& code, int short_co
 }
 
 // `size` value bits -> the coefficient (size <= 11; at most 27 bits since the refill in jpge_symbol); false: the data ended
-template <class Fetch>
-JPGE_HD bool jpge_value(JpgeReader<Fetch>& r, int size, int32_t& v)
+template <class Fetch, int Mode>
+JPGE_HD bool jpge_value(JpgeReader<Fetch, Mode>& r, int size, int32_t& v)
 {
     v = 0;
     if (!size) return true;
     const int32_t bits = (int32_t)r.peek(size);
     v = bits < (1 << (size - 1)) ? bits - (1 << size) + 1 : bits;
     return r.drop(size);
+}
+
+// ---- the rules of a block, for the interval loop below and for jps_unit (jpeg_split.h) ----
+// the component of block j of an MCU whose first ny blocks are component 0's
+JPGE_HD int jpge_component(int j, int ny) { return j < ny ? 0 : (j - ny + 1 > 2 ? 2 : j - ny + 1); }
+// a DC symbol is the size of the difference
+JPGE_HD bool jpge_dc_sound(int s) { return s <= 11; }
+// The AC symbol rs with the block at zigzag position k -> status code.  JPGE_OK: k is where the value goes and `size` its bits; size 0:
+// no value follows, and k is 64 after the end-of-block symbol, 16 further after ZRL.
+JPGE_HD int jpge_ac_step(int rs, int& k, int& size)
+{
+    const int run = rs >> 4;
+    size = rs & 15;
+    if (size > 10 || (size == 0 && run != 0 && run != 15)) return JPGE_BAD_SYMBOL;
+    if (rs == 0) { k = 64; return JPGE_OK; }
+    k += run + (size == 0);  // the zeros; ZRL is sixteen of them and must leave room for a value
+    return k > 63 ? JPGE_OVERRUN : JPGE_OK;
 }
 
 // One restart interval: the MCUs [first_mcu, first_mcu + mcus) of a file from the bytes [start, end) of its scan.  codes[2c], codes[2c + 1]:
@@ -170,15 +214,15 @@ JPGE_HD int jpge_interval(const Fetch& in, uint32_t start, uint32_t end, bool en
                           uint32_t first_mcu, uint32_t mcus, Sink& sink)
 {
     const int short_code = ended_by_rst ? JPGE_RESTART : JPGE_TRUNCATED;
-    JpgeReader<Fetch> r(in, start, end);
+    JpgeReader<Fetch, JPGE_WAVE> r(in, start, end);
     uint32_t pred[3] = { 0u, 0u, 0u };  // (unsigned: a crafted file may wrap it)
     for (uint32_t m = 0; m < mcus; m++)
         for (int j = 0; j < bpm; j++) {
-            const int c = j < ny ? 0 : (j - ny + 1 > 2 ? 2 : j - ny + 1);
+            const int c = jpge_component(j, ny);
             const JpgeCode& ac_code = *codes[2 * c + 1];  // (read once per block, not once per symbol)
             int s = jpge_symbol(r, *codes[2 * c], short_code);
             if (s < 0) return -s;
-            if (s > 11) return JPGE_BAD_SYMBOL;
+            if (!jpge_dc_sound(s)) return JPGE_BAD_SYMBOL;
             int32_t v;
             if (!jpge_value(r, s, v)) return short_code;
             pred[c] += (uint32_t)v;
@@ -186,12 +230,8 @@ JPGE_HD int jpge_interval(const Fetch& in, uint32_t start, uint32_t end, bool en
             for (int k = 1; k < 64;) {
                 const int rs = jpge_symbol(r, ac_code, short_code);
                 if (rs < 0) return -rs;
-                const int run = rs >> 4;
-                s = rs & 15;
-                if (s > 10 || (s == 0 && run != 0 && run != 15)) return JPGE_BAD_SYMBOL;
-                if (rs == 0) break;
-                k += run + (s == 0);  // the zeros; ZRL is sixteen of them and must leave room for a value
-                if (k > 63) return JPGE_OVERRUN;
+                const int rc = jpge_ac_step(rs, k, s);
+                if (rc != JPGE_OK) return rc;
                 if (s) {
                     if (!jpge_value(r, s, v)) return short_code;
                     sink.put(k, (int16_t)v);

@@ -1,9 +1,9 @@
 // jpeg_split.h -- the core of the split JPEG decode (include/gsraster_jpeg_split.h, rules 1 to 4 and 6): where a subsequence begins,
-// a bit reader that knows where it stands in the stuffed bytes, the decoder's state and its packed form, one decoding unit, and the
-// run of a decoder through one subsequence.  Host and device: jpeg_split.hip gives every lane a decoder of its own,
-// tools/jpeg_split_check.cpp emulates the lanes one after another under sanitizers.  The tables (JpgeCode, jpge_build), the marker
-// classes and the status codes are jpeg_entropy.h's; its reader keeps its words in scalar registers for 64 lanes in one state, so
-// the reader here is its logic again, per lane.
+// the decoder's state and its packed form, one decoding unit, and the run of a decoder through one subsequence.  Host and device:
+// jpeg_split.hip gives every lane a decoder of its own, tools/jpeg_split_check.cpp emulates the lanes one after another under
+// sanitizers.  The tables (JpgeCode, jpge_build), the marker classes, the status codes, the bit reader, the symbol, the value and the
+// rules of a block are jpeg_entropy.h's; the reader runs here in its lane mode (JPGE_LANE): nothing made uniform, and it knows where it
+// stands in the stuffed bytes.
 //
 //   Fetch   uint8_t operator()(uint32_t at)  byte `at` of the scan, at < the scan's length; every lane asks for a byte of its own
 //   Sink    bool full(int k)                  true: decode no further unit (k = the state's: the interval's last block is complete)
@@ -66,80 +66,8 @@ JPGE_HD JpsState jps_unpack(uint32_t w, uint32_t begin, int bpm)
     return s;
 }
 
-// The bits from a position on, up to the interval's end.  acc holds nbits bits, right-aligned, of which the last `fake` were made up
-// behind the end of the data; `pairs`: bit i = the i-th last byte taken into acc was the FF of an FF 00 pair (two bytes of the scan).
 template <class Fetch>
-struct JpsReader {
-    Fetch in;
-    uint32_t pos, end;
-    uint64_t acc;
-    uint32_t pairs;
-    int nbits, fake;
-    bool ended;
-    JPGE_HD JpsReader(const Fetch& f, uint32_t byte, int bit, uint32_t stop) : in(f), pos(byte), end(stop), acc(0), pairs(0), nbits(0), fake(0), ended(false)
-    {
-        refill();
-        nbits -= bit & 7;  // (nbits > 56)
-    }
-    JPGE_HD void refill()  // -> nbits > 56; every round takes a byte of the data or makes one up
-    {
-        while (nbits <= 56) {
-            uint32_t b = 0, pair = 0;
-            bool have = false;
-            if (!ended && pos < end) {
-                b = in(pos);
-                if (b != 0xFFu) { pos++; have = true; }
-                else if (pos + 1 < end && in(pos + 1) == 0u) { pos += 2; have = true; pair = 1; }
-                else ended = true;  // a fill byte, or the interval's last byte: the data ends here
-            }
-            if (!have) { b = 0; fake += 8; }
-            acc = (acc << 8) | b;
-            pairs = (pairs << 1) | pair;
-            nbits += 8;
-        }
-    }
-    JPGE_HD uint32_t peek(int n) const { return (uint32_t)(acc >> (nbits - n)) & ((1u << n) - 1u); }  // n <= 16 <= nbits
-    JPGE_HD bool drop(int n) { nbits -= n; return nbits >= fake; }                                       // false: made-up bits were used
-    JPGE_HD int real() const { return nbits - fake; }
-    // where the next bit lies; meaningful while no made-up bit has been used
-    JPGE_HD void where(uint32_t& byte, int& bit) const
-    {
-        const int held = (nbits + 7) >> 3, made = fake >> 3, live = held > made ? held - made : 0;  // bytes of acc not fully consumed; the made-up ones; the data's
-        const uint32_t twice = (uint32_t)__builtin_popcount((pairs >> made) & ((1u << live) - 1u));  // (live <= 8)
-        byte = pos - (uint32_t)live - twice;
-        bit = (8 - (nbits & 7)) & 7;
-    }
-};
-
-// the next symbol -> 0 .. 255, or -1
-template <class Fetch>
-JPGE_HD int jps_symbol(JpsReader<Fetch>& r, const JpgeCode& code)
-{
-    if (r.nbits < 32) r.refill();
-    const uint32_t w = r.peek(16);
-    const uint32_t quick = code.look[w >> (16 - JPGE_LOOK_BITS)];
-    int n = (int)(quick >> 8), sym = (int)(quick & 255u);
-    if (!n) {
-        for (n = JPGE_LOOK_BITS + 1; n <= 16; n++) {
-            const int32_t c = (int32_t)(w >> (16 - n));
-            if (c <= code.maxcode[n]) {
-                sym = (int)code.values[(uint32_t)(c + code.delta[n]) & 255u];
-                break;
-            }
-        }
-        if (n > 16) return -1;
-    }
-    return r.drop(n) ? sym : -1;
-}
-template <class Fetch>
-JPGE_HD bool jps_value(JpsReader<Fetch>& r, int size, int32_t& v)  // as jpge_value
-{
-    v = 0;
-    if (!size) return true;
-    const int32_t bits = (int32_t)r.peek(size);
-    v = bits < (1 << (size - 1)) ? bits - (1 << size) + 1 : bits;
-    return r.drop(size);
-}
+using JpsReader = JpgeReader<Fetch, JPGE_LANE>;  // from (byte, bit) of a state on: JpsReader(in, s.byte, stop, s.bit)
 
 // The file's lookup tables: entry 2c is component c's DC table, 2c + 1 its AC table; slot e of `slots` (four bits each) is the entry's
 // place in `base`, so a table two components share is stored once and a lane finds its table by arithmetic, not through an array of
@@ -154,28 +82,22 @@ struct JpsTables {
 template <class Fetch, class Sink>
 JPGE_HD bool jps_unit(JpsReader<Fetch>& r, const JpsTables& codes, int ny, int bpm, int& j, int& k, Sink& sink)
 {
-    const int c = j < ny ? 0 : (j - ny + 1 > 2 ? 2 : j - ny + 1);
+    const int c = jpge_component(j, ny);
     int32_t v;
+    int s;
     if (k == 0) {
-        const int s = jps_symbol(r, codes.at(2 * c));
-        if (s < 0 || s > 11 || !jps_value(r, s, v)) return false;
+        s = jpge_symbol(r, codes.at(2 * c), JPGE_TRUNCATED);  // (which code it fails with does not matter here: any negative result fails)
+        if (s < 0 || !jpge_dc_sound(s) || !jpge_value(r, s, v)) return false;
         sink.dc(v);
         k = 1;
         return true;
     }
-    const int rs = jps_symbol(r, codes.at(2 * c + 1));
-    if (rs < 0) return false;
-    const int run = rs >> 4, s = rs & 15;
-    if (s > 10 || (s == 0 && run != 0 && run != 15)) return false;
-    if (rs == 0) k = 64;  // EOB
-    else {
-        k += run + (s == 0);  // the zeros; ZRL is sixteen of them and must leave room for a value
-        if (k > 63) return false;
-        if (s) {
-            if (!jps_value(r, s, v)) return false;
-            sink.ac(k, v);
-            k++;
-        }
+    const int rs = jpge_symbol(r, codes.at(2 * c + 1), JPGE_TRUNCATED);
+    if (rs < 0 || jpge_ac_step(rs, k, s) != JPGE_OK) return false;
+    if (s) {
+        if (!jpge_value(r, s, v)) return false;
+        sink.ac(k, v);
+        k++;
     }
     if (k == 64) { k = 0; j = j + 1 < bpm ? j + 1 : 0; }
     return true;
@@ -188,7 +110,7 @@ template <class Fetch, class Sink>
 JPGE_HD void jps_run(const Fetch& in, JpsState& s, uint32_t limit, uint32_t stop, const JpsTables& codes, int ny, int bpm, Sink& sink)
 {
     if (!s.ok || s.byte >= limit) return;
-    JpsReader<Fetch> r(in, s.byte, s.bit, stop);
+    JpsReader<Fetch> r(in, s.byte, stop, s.bit);
     const uint32_t most = 8u * (limit - s.byte);  // (limit - s.byte: a subsequence and the tail of a unit, far below 2^29)
     for (uint32_t n = 0; n < most; n++) {
         if (s.byte >= limit || sink.full(s.k)) return;
@@ -291,6 +213,6 @@ JPGE_HD bool jps_write(Fetch& in, const JpsInterval& iv, uint32_t x, const uint3
         return w != JPS_NO_STATE && w == entry[x];
     }
     if (fb + place.begun != iv.total || s.k) return false;
-    JpsReader<Fetch> rest(in, s.byte, s.bit, iv.cut.end);
+    JpsReader<Fetch> rest(in, s.byte, iv.cut.end, s.bit);
     return rest.real() < 8;  // a whole byte behind the last MCU is the serial decoder's RESTART
 }

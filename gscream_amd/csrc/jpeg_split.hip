@@ -1,6 +1,6 @@
 // jpeg_split.hip -- baseline JPEG decoding with an interval's scan split at self-synchronisation points: the rules, the launches and
-// the repair are in include/gsraster_jpeg_split.h in full; the core (where a subsequence begins, the per-lane bit reader, the state, one
-// lane's part of every pass) is jpeg_split.h, which tools/jpeg_split_check.cpp runs on the host under sanitizers over the same corpus.
+// the repair are in include/gsraster_jpeg_split.h in full; the core (where a subsequence begins, the state, one lane's part of every pass, over
+// jpeg_entropy.h's bit reader in its lane mode) is jpeg_split.h, which tools/jpeg_split_check.cpp runs on the host under sanitizers over the same corpus.
 // Here one lane decodes one subsequence with a state of its own (in jpeg_decode.hip's entropy kernel 64 lanes hold one state); the
 // file's six lookup tables sit in LDS (8.5 KB) and are read divergently; a lane's bytes come through one aligned dword it keeps in a
 // register.  The launches run inside jpeg_decode.hip's own sequence (jpeg_decode_launch.h), between its markers and entropy kernels:
@@ -67,38 +67,20 @@ static JsCarve js_carve(void* base, int nintervals, size_t scan_bytes, int B)
 // byte `at` of a file's scan through the aligned dword that holds it, kept in a register; a dword that reaches over the scan's end is
 // read byte by byte
 struct JsFetch {
-    const uint8_t* aligned;  // the scan's first byte, rounded down to a dword of `bytes`
-    uint32_t shift, limit;   // the scan starts at aligned + shift and ends at aligned + limit
-    uint32_t base, word;     // base 0xffffffff = nothing loaded
+    JdScan scan;
+    uint32_t base, word;  // base 0xffffffff = nothing loaded
     __device__ uint8_t operator()(uint32_t at)
     {
-        const uint32_t q = at + shift;
+        const uint32_t q = at + scan.shift;
         if ((q & ~3u) != base) {
             base = q & ~3u;
-            uint32_t v = 0;
-            if (base < limit && limit - base >= 4u) v = *(const uint32_t*)(aligned + base);
-            else
-                for (uint32_t j = 0; j < 4u && base < limit && j < limit - base; j++) v |= (uint32_t)aligned[base + j] << (8u * j);
-            word = v;
+            word = scan.dword(base);
         }
         return (uint8_t)(word >> (8u * (q & 3u)));
     }
 };
-__device__ __forceinline__ JsFetch js_fetch(const uint8_t* bytes, const gsr_jpeg_file& fl)
-{
-    const uint8_t* scan = bytes + fl.scan_offset;
-    const uint32_t shift = (uint32_t)((uintptr_t)scan & 3u);
-    return JsFetch{scan - shift, shift, shift + fl.scan_length, 0xffffffffu, 0u};
-}
+__device__ __forceinline__ JsFetch js_fetch(const uint8_t* bytes, const gsr_jpeg_file& fl) { return JsFetch{jd_scan(bytes, fl), 0xffffffffu, 0u}; }
 
-// the file that owns interval i and is sound so far, or -1 (as the entropy kernel decides it)
-__device__ __forceinline__ int js_owner(int i, const gsr_jpeg_file* files, int nfiles, const JdWorkspace& ws, const int32_t* status)
-{
-    const int f = ws.ivl_owner[i];
-    if ((uint32_t)f >= (uint32_t)nfiles || status[2 * f] != GSR_JPEG_DECODE_OK) return -1;
-    if (i < files[f].first_interval || i >= files[f].first_interval + files[f].intervals) return -1;
-    return f;
-}
 // interval i of file fl: its bytes cut by B, its blocks
 struct JsPiece {
     JpsCut cut;
@@ -108,16 +90,8 @@ struct JsPiece {
 __device__ __forceinline__ JsPiece js_piece(JsFetch& in, const gsr_jpeg_file& fl, int i, const JdWorkspace& ws, uint32_t B)
 {
     const JdGeometry g = jd_geometry(fl);
-    const uint32_t k = (uint32_t)(i - fl.first_interval);
-    // [start, end) lies in the scan: the markers kernel wrote positions of bytes it read
-    const uint32_t start = min(ws.ivl_start[i], fl.scan_length), end = min(ws.ivl_end[i], fl.scan_length);
-    JsPiece p;
-    p.cut = jps_cut(in, start, max(start, end), B);
-    p.first_mcu = k * g.per;
-    p.total = min(g.per, g.mcus - p.first_mcu) * (uint32_t)g.bpm;
-    p.ny = g.ny;
-    p.bpm = g.bpm;
-    return p;
+    const JdPiece q = jd_piece(fl, g, i, ws);
+    return JsPiece{jps_cut(in, q.start, max(q.start, q.end), B), q.first_mcu, q.mcus * (uint32_t)g.bpm, g.ny, g.bpm};
 }
 
 // ---- classify ----
@@ -128,7 +102,7 @@ __global__ void __launch_bounds__(1024) jpeg_split_classify_kernel(const uint8_t
     const int per = (nintervals + 1023) / 1024, i0 = (int)threadIdx.x * per;
     for (int i = i0; i < i0 + per && i < nintervals; i++) {
         uint32_t count = 0;
-        const int f = js_owner(i, files, nfiles, ws, status);
+        const int f = jd_owner(i, files, nfiles, ws, status);
         if (f >= 0) {
             const gsr_jpeg_file fl = files[f];
             JsFetch in = js_fetch(bytes, fl);
@@ -168,25 +142,11 @@ __device__ __forceinline__ int js_chunk_interval(unsigned long long chunk, int n
     return lo;
 }
 
-struct JsTeam {
-    int lane, lanes;
-    __device__ void sync() { __syncthreads(); }
-};
 // the file's lookup tables, built by the workgroup together (all its threads call); false: a table is unsound
-__device__ __forceinline__ bool js_build(JsTeam tm, JpgeCode* codes, JpsTables& use, const gsr_jpeg_file& fl, const JpgeHuffman* huffman)
+__device__ __forceinline__ bool js_build(JdTeam tm, JpgeCode* codes, JpsTables& use, const gsr_jpeg_file& fl, const JpgeHuffman* huffman)
 {
-    bool sound = true;
-    uint32_t slots = 0;
-    for (int c = 0; c < fl.C; c++) {
-        // a table two components share is built once
-        const bool dc_again = c > 0 && fl.dc[c] == fl.dc[c - 1], ac_again = c > 0 && fl.ac[c] == fl.ac[c - 1];
-        uint32_t dc = 2u * (uint32_t)c, ac = dc + 1u;
-        if (dc_again) dc = (slots >> (8 * (c - 1))) & 15u;
-        else sound = jpge_build(tm, codes[dc], huffman + fl.dc[c]) && sound;
-        if (ac_again) ac = (slots >> (8 * (c - 1) + 4)) & 15u;
-        else sound = jpge_build(tm, codes[ac], huffman + fl.ac[c]) && sound;
-        slots |= (dc | ac << 4) << (8 * c);
-    }
+    uint32_t slots;
+    const bool sound = jd_build(tm, codes, fl, huffman, slots);
     if (fl.C == 1) slots |= slots << 8 | slots << 16;  // (j is 0 in a grey file: never followed)
     use.base = codes;
     use.slots = slots;
@@ -203,11 +163,11 @@ __global__ void __launch_bounds__(JS_CHUNK) jpeg_split_sync_kernel(const uint8_t
     uint32_t c = 0;
     const int i = js_chunk_interval(blockIdx.x, nintervals, t, &c);
     if (i < 0) return;
-    const int f = js_owner(i, files, nfiles, ws, status);
+    const int f = jd_owner(i, files, nfiles, ws, status);
     if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
     JpsTables use;
-    if (!js_build(JsTeam{tid, JS_CHUNK}, codes, use, fl, huffman)) return;  // (the write pass finds the same and hands the interval over)
+    if (!js_build(JdTeam{tid, JS_CHUNK}, codes, use, fl, huffman)) return;  // (the write pass finds the same and hands the interval over)
     JsFetch in = js_fetch(bytes, fl);
     const JsPiece p = js_piece(in, fl, i, ws, B);
     const JpsInterval iv = {p.cut, use, p.ny, p.bpm, p.total};
@@ -232,11 +192,11 @@ __global__ void __launch_bounds__(64) jpeg_split_walk_kernel(const uint8_t* __re
     __shared__ JpgeCode codes[6];
     const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (!t.split[i] || t.count[i] <= JS_CHUNK) return;  // (one chunk: subsequence 0 started from the true state)
-    const int f = js_owner(i, files, nfiles, ws, status);
+    const int f = jd_owner(i, files, nfiles, ws, status);
     if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
     JpsTables use;
-    if (!js_build(JsTeam{lane, 64}, codes, use, fl, huffman) || lane) return;
+    if (!js_build(JdTeam{lane, 64}, codes, use, fl, huffman) || lane) return;
     JsFetch in = js_fetch(bytes, fl);
     const JsPiece p = js_piece(in, fl, i, ws, B);
     const JpsInterval iv = {p.cut, use, p.ny, p.bpm, p.total};
@@ -250,7 +210,7 @@ __global__ void __launch_bounds__(JS_CHUNK) jpeg_split_pairs_kernel(const uint8_
     uint32_t c = 0;
     const int i = js_chunk_interval(blockIdx.x, nintervals, t, &c);
     if (i < 0) return;
-    const int f = js_owner(i, files, nfiles, ws, status);
+    const int f = jd_owner(i, files, nfiles, ws, status);
     if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
     JsFetch in = js_fetch(bytes, fl);
@@ -308,11 +268,11 @@ __global__ void __launch_bounds__(JS_CHUNK) jpeg_split_write_kernel(const uint8_
     uint32_t c = 0;
     const int i = js_chunk_interval(blockIdx.x, nintervals, t, &c);
     if (i < 0) return;
-    const int f = js_owner(i, files, nfiles, ws, status);
+    const int f = jd_owner(i, files, nfiles, ws, status);
     if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
     JpsTables use;
-    if (!js_build(JsTeam{tid, JS_CHUNK}, codes, use, fl, huffman)) {
+    if (!js_build(JdTeam{tid, JS_CHUNK}, codes, use, fl, huffman)) {
         if (tid == 0) t.only[i] = 1;  // the entropy kernel reports the table
         return;
     }
@@ -347,21 +307,21 @@ __global__ void __launch_bounds__(256) jpeg_split_dc_kernel(const gsr_jpeg_file*
 {
     const int i = (int)blockIdx.x, tid = (int)threadIdx.x;
     if (!t.split[i] || t.only[i]) return;
-    const int f = js_owner(i, files, nfiles, ws, status);
+    const int f = jd_owner(i, files, nfiles, ws, status);
     if (f < 0) return;
     const gsr_jpeg_file fl = files[f];
     const JdGeometry g = jd_geometry(fl);
-    const uint32_t first_mcu = (uint32_t)(i - fl.first_interval) * g.per, mcus = min(g.per, g.mcus - first_mcu);
+    const uint32_t first_mcu = jd_piece(fl, g, i, ws).first_mcu, mcus = jd_piece(fl, g, i, ws).mcus;
     int16_t* coef = (int16_t*)(ws.area + fl.coef_offset) + (size_t)first_mcu * (size_t)g.bpm * 64;
     const uint32_t per = (mcus + 255u) / 256u, m0 = (uint32_t)tid * per, m1 = min(mcus, m0 + per);
     uint32_t sum[3] = {0u, 0u, 0u};
     for (uint32_t m = m0; m < m1; m++)
-        for (int j = 0; j < g.bpm; j++) sum[j < g.ny ? 0 : j - g.ny + 1] += (uint32_t)(int32_t)coef[((size_t)m * g.bpm + j) * 64];
+        for (int j = 0; j < g.bpm; j++) sum[jpge_component(j, g.ny)] += (uint32_t)(int32_t)coef[((size_t)m * g.bpm + j) * 64];
     gsr_block_scan_excl<256>(sum);  // (integer sums modulo 2^32: the order of the additions does not show)
     for (uint32_t m = m0; m < m1; m++)
         for (int j = 0; j < g.bpm; j++) {
             int16_t* dc = coef + ((size_t)m * g.bpm + j) * 64;
-            uint32_t& pred = sum[j < g.ny ? 0 : j - g.ny + 1];
+            uint32_t& pred = sum[jpge_component(j, g.ny)];
             pred += (uint32_t)(int32_t)*dc;
             *dc = (int16_t)(uint16_t)pred;
         }
