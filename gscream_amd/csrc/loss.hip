@@ -17,6 +17,11 @@
 // (d/d mu1, d/d E[x^2], d/d E[xy] of the weighted map); the backward filters those with the same two passes and
 // contracts them with the images:  dL/dx = G*(d_mu1) + 2x G*(d_E11) + y G*(d_E12)  (+ the L1 sign term).
 // Sums are reduced per workgroup and finished by one block in a fixed order: bit-reproducible.
+// The FORWARD filters in fp64 (both passes, the row-filtered planes in LDS included) and rounds once, at A, B, Cc, D: on a flat
+// region sigma1^2 + sigma2^2 and sigma12 are exactly 0 and an fp32 filter leaves the rounding error of numbers near 1 over C2 = 9e-4
+// there -- the same error at every pixel of the region, so the mean keeps it (7e-6 of the SSIM term on a frame a tenth of which is
+// two flats; eager fp32 has 5e-6).  Zeros stay exact and nothing depends on a neighbour's data, which a shift by a local mean
+// would give up.  The backward's planes are well conditioned and stay fp32.
 // HBM traffic per pixel-channel: forward 8 B in (+4/C weight) + 12 B out, backward 20 B in + 4 B out.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,7 +59,7 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
 {
     const float* GSL_G = taps.g;
     __shared__ float sx[GSL_HH][GSL_HW + 1], sy[GSL_HH][GSL_HW + 1];
-    __shared__ float hx[4][GSL_HH][GSL_TW];
+    __shared__ double hx[4][GSL_HH][GSL_TW];
     const int t = threadIdx.x, ch = blockIdx.z;
     const int x0 = blockIdx.x * GSL_TW, y0 = blockIdx.y * GSL_TH;
     const size_t plane = (size_t)H * W;
@@ -86,15 +91,15 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
         for (int k = 0; k < 14; k++) { xs[k] = sx[r][c + k]; ys[k] = sy[r][c + k]; }
         // FOUR filtered quantities, not five: the map needs sigma1^2 + sigma2^2 = E[x^2 + y^2] - mu1^2 - mu2^2 and sigma12 = E[xy] - mu1 mu2,
         // never E[x^2] and E[y^2] apart (and d ssim / d E[x^2] = d ssim / d E[x^2 + y^2]: the backward's planes are unchanged)
-        float s1[4] = { 0, 0, 0, 0 }, s2[4] = { 0, 0, 0, 0 }, sS[4] = { 0, 0, 0, 0 }, s12[4] = { 0, 0, 0, 0 };
+        double s1[4] = { 0, 0, 0, 0 }, s2[4] = { 0, 0, 0, 0 }, sS[4] = { 0, 0, 0, 0 }, s12[4] = { 0, 0, 0, 0 };
 #pragma unroll
         for (int k = 0; k < 14; k++) {
-            const float x = xs[k], y = ys[k], ss = x * x + y * y, xy = x * y;
+            const double x = xs[k], y = ys[k], ss = x * x + y * y, xy = x * y;
 #pragma unroll
             for (int o = 0; o < 4; o++) {
                 const int tap = k - o;
                 if (tap >= 0 && tap < 11) {
-                    const float g = GSL_G[tap];
+                    const double g = GSL_G[tap];
                     s1[o] += g * x; s2[o] += g * y; sS[o] += g * ss; s12[o] += g * xy;
                 }
             }
@@ -108,7 +113,7 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
     double sums[2] = { 0.0, 0.0 };  // |x - y| m, ssim m
     // vertical pass: a thread finishes two vertically adjacent pixels from a 12-row register window
     const int vc = t % GSL_TW, vr = (t / GSL_TW) * 2;
-    float col[4][12];
+    double col[4][12];
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -117,18 +122,19 @@ __global__ void __launch_bounds__(256) gsl_forward_kernel(int H, int W, const fl
     for (int half = 0; half < 2; half++) {
         const int r = vr + half, c = vc;
         const int px = x0 + c, py = y0 + r;
-        float mu1 = 0.f, mu2 = 0.f, eS = 0.f, e12 = 0.f;
+        double m1 = 0.0, m2 = 0.0, eS = 0.0, e12 = 0.0;
 #pragma unroll
         for (int k = 0; k < 11; k++) {
-            const float g = GSL_G[k];
-            mu1 += g * col[0][half + k]; mu2 += g * col[1][half + k];
+            const double g = GSL_G[k];
+            m1 += g * col[0][half + k]; m2 += g * col[1][half + k];
             eS += g * col[2][half + k]; e12 += g * col[3][half + k];
         }
         if (px < W && py < H) {
             const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;  // loss_utils.py:153-154
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float sig12 = e12 - mu12;
-            const float A = 2.f * mu12 + C1, B = 2.f * sig12 + C2, Cc = mu1_sq + mu2_sq + C1, D = (eS - mu1_sq - mu2_sq) + C2;
+            const double m1_sq = m1 * m1, m2_sq = m2 * m2, m12 = m1 * m2;
+            const float mu1 = (float)m1, mu2 = (float)m2;
+            const float A = (float)(2.0 * m12 + (double)C1), B = (float)(2.0 * (e12 - m12) + (double)C2);
+            const float Cc = (float)(m1_sq + m2_sq + (double)C1), D = (float)((eS - m1_sq - m2_sq) + (double)C2);
             const float inv = 1.0f / (Cc * D);
             const float ssim = A * B * inv;
             const float m = weight ? weight[(size_t)py * W + px] : 1.0f;
